@@ -20,7 +20,12 @@ Workload: Kuhn-cube mesh n=119 -> 10,110,954 P1 tets, 1,728,0
     BASELINE.md §3), rank 0 at N=1 only. Measured ratio: the CPU's assembly + 50 iterations against the GPU's
     assembly + 50 timed iterations; the whole-solve wall is projected from the CPU iteration rate (labelled so).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run measures the headline figure only: it assembles the system once, warms up, times the K steps (`value`,
+`ms_per_step`, the timed launch's own kernel time and roofline), writes the iterate with --dump-outputs and prints
+the line. DOFs/s, the STREAM ceilings and assembly roofline, the CPU baseline and the elasticity / matrix-free /
+reference-API / configs[4] / configs[1] companions are measured with --full, in the same JSON line.
 """
 from __future__ import annotations
 
@@ -109,7 +114,19 @@ def parse():
                          "Poisson; auto falls back to RCCL if its self-check fails) or the RCCL element partition")
     ap.add_argument("--dist-graph", type=int, default=50,
                     help="distributed path: capture k iterations (kernels + RCCL) per hipGraph, 0 = plain launches")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the DOFs/s passes (assembly + solve to rtol), the "
+                         "measured STREAM ceilings and the assembly roofline, the CPU baseline, and the elasticity / "
+                         "matrix-free / reference-API / configs[4] / configs[1] companions (each still under its own "
+                         "switch). Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed as DIR/<name>.npy: x, the PCG "
+                         "iterate after warmup + steps iterations (fp64, single-GPU runs)")
+    a = ap.parse_args()
+    if not a.full:   # a plain run measures the headline figure only
+        a.elastic = a.mixed = a.config1 = 0
+        a.no_cpu_baseline = True
+    return a
 
 
 def sync():
@@ -257,6 +274,8 @@ def main():
         os.environ.setdefault("MASTER_PORT", "29533")
         os.environ.setdefault("WORLD_SIZE", str(world))
         os.environ.setdefault("RANK", str(rank))
+        if a.dump_outputs:
+            raise SystemExit("--dump-outputs: single-GPU runs only (the distributed iterate stays partitioned)")
         from fem355 import dist
         return dist.bench_main(a, METRIC)
     torch.cuda.set_device(local)
@@ -276,7 +295,7 @@ def main():
     coords, tets = mesh.kuhn_cube(a.n, device=dev)
     if a.permute:
         coords, tets = permute_nodes(coords, tets, a.permute)
-    out = measure(a, a.kind, coords, tets, dev)
+    out = measure(a, a.kind, coords, tets, dev, full=a.full, dump=a.dump_outputs)
     if not a.no_cpu_baseline and rank == 0:
         attach_cpu_baseline(out, cpu_baseline(a.n, a.kind, a.cpu_iters, out["solve_iters"]))
     # BASELINE configs[2] beside the metric: the same steps on the 10M-tet linear-elasticity system (north_star:
@@ -615,9 +634,25 @@ def measure_reference_api(a, coords, tets, dev, ref):
             "solve_iters_fused_pipeline": ref["solve_iters"]}
 
 
-def measure(a, kind, coords, tets, dev):
-    """One single-GPU measurement of `kind` on the mesh: DOFs/s (assembly + solve to rtol, two passes) and the
-    fixed-iteration CG it/s with its roofline. Returns the bench dict (cpu_baseline None)."""
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array of the timed path's result as path/<name>.npy (fp64 as computed), at most 64 MB in
+    all: the 10M-tet systems' iterates whole, of a larger output the same seeded sample of entries in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    total, limit = sum(v.nbytes for v in arrays.values()), 64 << 20
+    for name, v in arrays.items():
+        if total > limit:
+            keep = np.random.default_rng(0).choice(v.size, int(v.size * (limit / total)), replace=False)
+            v = v.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
+def measure(a, kind, coords, tets, dev, full=True, dump=None):
+    """One single-GPU measurement of `kind` on the mesh: the fixed-iteration CG it/s with its roofline and, with
+    `full`, DOFs/s (assembly + solve to rtol, --dof-passes passes after a cold one), the measured STREAM ceilings and
+    the assembly roofline. `dump`: a directory for the timed path's result (dump_outputs). Returns the bench dict
+    (cpu_baseline None)."""
     M, N = tets.shape[0], coords.shape[0]
     if kind == "poisson":
         f, fixed = mesh.cube_poisson_case(coords)
@@ -637,7 +672,7 @@ def measure(a, kind, coords, tets, dev):
     # --pipelined 1: the pipelined persistent iteration where it applies (include/fem355.h FEM_TUNE_PK_GV)
     tune = (C.TUNE_DEFAULT | C.TUNE_PK_GV) if a.pipelined else None
 
-    def assemble_and_solve():
+    def assemble_and_solve(solve=True):
         t0 = time.perf_counter()
         c, t, ff, fx = coords, tets, f, fixed
         if a.reorder == "rcm":   # renumbered mesh, load and constraints (u maps back through inv)
@@ -654,6 +689,8 @@ def measure(a, kind, coords, tets, dev):
         t_asm = time.perf_counter() - t0
         A.check_singular()
         b = ff.reshape(-1).to(torch.float64).contiguous()
+        if not solve:   # the operator, weights and load of the timed steps only
+            return A, w, b, None, t_asm, 0.0
         tol = a.rtol * float(torch.sqrt(torch.dot(b, w * b)))
         sync()
         t0 = time.perf_counter()
@@ -662,20 +699,21 @@ def measure(a, kind, coords, tets, dev):
         sync()
         return A, w, b, res, t_asm, time.perf_counter() - t0
 
-    A, w, b, res, t_asm_cold, t_solve_cold = assemble_and_solve()
+    A, w, b, res, t_asm_cold, t_solve_cold = assemble_and_solve(solve=full)
     res_cold = res
     passes = []
-    for _ in range(max(a.dof_passes, 1)):
+    for _ in range(max(a.dof_passes, 1) if full else 0):
         del A, w, b, res
         A, w, b, res, t_asm, t_solve = assemble_and_solve()
         assert res.iterations == res_cold.iterations and res.status == res_cold.status
         passes.append((t_asm, t_solve))
-    # steady state: the median pass by its assembly + solve total (a measured pass: dofs_per_s, assembly_ms and
-    # solve_ms all come from it); the medians of the assembly times and of the solve times taken separately (they
-    # may come from different passes) are reported beside it
-    t_asm, t_solve = sorted(passes, key=lambda p: p[0] + p[1])[len(passes) // 2]
-    t_asm_med = sorted(p[0] for p in passes)[len(passes) // 2]
-    t_solve_med = sorted(p[1] for p in passes)[len(passes) // 2]
+    if full:
+        # steady state: the median pass by its assembly + solve total (a measured pass: dofs_per_s, assembly_ms and
+        # solve_ms all come from it); the medians of the assembly times and of the solve times taken separately
+        # (they may come from different passes) are reported beside it
+        t_asm, t_solve = sorted(passes, key=lambda p: p[0] + p[1])[len(passes) // 2]
+        t_asm_med = sorted(p[0] for p in passes)[len(passes) // 2]
+        t_solve_med = sorted(p[1] for p in passes)[len(passes) // 2]
 
     # ---- fixed-iteration timing (the metric)
     run = system.PcgRunner(A, b, w, tol=0.0, schedule=a.schedule, tune=tune)
@@ -705,6 +743,8 @@ def measure(a, kind, coords, tets, dev):
               system.SCHED_PERSIST: "k_pcg_persist3" if A.bs == 3 else "k_pcg_persist"}[run.effective_schedule()]
     if pipelined:
         kernel = "k_pcg_persist_gv"
+    if dump:   # what a caller of the timed path receives: the iterate after warmup + steps iterations
+        dump_outputs(dump, {"x": run.x})
     run.close()
 
     # per launch of the measured kernel: one SpMV (3-kernel / deferred) or one whole iteration (persistent: the
@@ -719,13 +759,13 @@ def measure(a, kind, coords, tets, dev):
     # measured iteration time; the SpMV frac uses the SpMV launch alone where the schedule has one
     iter_ms = spmv_ms if persist else spmv_ms + ms[1] / max(cnt[1], 1) + ms[2] / max(cnt[2], 1)
     s8d = s8d_models(A.n, A.g.nnz * A.bs * A.bs, spmv_ms, iter_ms, persist)
-    ceiling = system.stream_ceiling(dev)
+    ceiling = system.stream_ceiling(dev) if full else None
     # the assembly's value kernel alone, outside every timed region: one launch on a fresh matrix of the same
     # pattern (the store path of the assembly passes) between hip events on the library's stream (torch's current
     # stream), against SURVEY §8(d)'s B_asm = 112 M + 8 nnz (conn + gathered coordinates in, every value written
     # once; nnz counts scalar values, so x bs^2 for the block system). Skipped with --reorder (renumbered mesh).
     asm_roof = None
-    if a.reorder != "rcm":
+    if full and a.reorder != "rcm":
         A2 = system.SellMatrix(A.g, A.bs)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         sync()
@@ -741,6 +781,21 @@ def measure(a, kind, coords, tets, dev):
                     "model": "SURVEY 8(d) B_asm = 112 M + 8 nnz (values only; the pattern build excluded)"}
         del A2
     workload_key = f"kuhn{a.n}_{kind}"
+    # the DOFs/s passes and what else takes runs of its own (--full)
+    dofs = {
+        "dofs_per_s": A.n / (t_asm + t_solve),
+        "assembly_ms": t_asm * 1e3,
+        "solve_ms": t_solve * 1e3,
+        "dofs_passes_ms": [[round(x * 1e3, 4), round(y * 1e3, 4)] for x, y in passes],
+        "dofs_per_s_split_medians": A.n / (t_asm_med + t_solve_med),
+        "assembly_ms_median": t_asm_med * 1e3,
+        "solve_ms_median": t_solve_med * 1e3,
+        "dofs_per_s_cold": A.n / (t_asm_cold + t_solve_cold),
+        "assembly_ms_cold": t_asm_cold * 1e3,
+        "solve_ms_cold": t_solve_cold * 1e3,
+        "solve_iters": res.iterations,
+    } if full else {}
+    stream = {"stream_ceiling_GBps": ceiling, "frac_of_stream_read": achieved / ceiling["read"]} if full else {}
     out = {
         "metric": METRIC,
         "value": a.steps / dt,
@@ -758,21 +813,11 @@ def measure(a, kind, coords, tets, dev):
                    "tets": M, "nodes": N, "dofs": A.n, "nnz_blocks": A.g.nnz, "format": "SELL-64 fp64 values, " + ("int16 column deltas" if A.use16 else "int32 cols")
                    + (f", slice-uniform deltas in {n_uni} of {n_sl} slices" if (persist and n_uni) else ""),
                    "parallelism": "single GPU"},
-        "dofs_per_s": A.n / (t_asm + t_solve),
-        "assembly_ms": t_asm * 1e3,
-        "solve_ms": t_solve * 1e3,
-        "dofs_passes_ms": [[round(x * 1e3, 4), round(y * 1e3, 4)] for x, y in passes],
-        "dofs_per_s_split_medians": A.n / (t_asm_med + t_solve_med),
-        "assembly_ms_median": t_asm_med * 1e3,
-        "solve_ms_median": t_solve_med * 1e3,
-        "dofs_per_s_cold": A.n / (t_asm_cold + t_solve_cold),
-        "assembly_ms_cold": t_asm_cold * 1e3,
-        "solve_ms_cold": t_solve_cold * 1e3,
-        "solve_iters": res.iterations,
+        **dofs,
         "mesh_numbering": ("random (seed %d)" % a.permute if a.permute else "lexicographic")
         + (", device RCM renumbering in every assembly pass" if a.reorder == "rcm" else ""),
         "reorder_ms": (sorted(reorder_ms)[len(reorder_ms) // 2] if reorder_ms else None),
-        "solve_status": res.status,
+        **({"solve_status": res.status} if full else {}),
         "pipelined": pipelined,
         "kernel_ms": ({"persist_iteration": spmv_ms, "iterations_per_launch": a.steps} if persist else
                       {"spmv_dot": spmv_ms, "update": ms[1] / max(cnt[1], 1), "pupdate": ms[2] / max(cnt[2], 1),
@@ -783,10 +828,8 @@ def measure(a, kind, coords, tets, dev):
                      if traffic_from_profiles(workload_key, kernel, alg) is not None else None,
                      "kernel": kernel, "algorithmic_bytes": alg,
                      "per": "iteration (whole PCG iteration in the persistent kernel)" if persist else "SpMV launch",
-                     "stream_ceiling_GBps": ceiling, "frac_of_stream_read": achieved / ceiling["read"],
-                     "s8d": s8d},
-        "assembly_roofline": asm_roof,
-        "cpu_baseline": None,
+                     **stream, "s8d": s8d},
+        **({"assembly_roofline": asm_roof, "cpu_baseline": None} if full else {}),
     }
     return out
 

@@ -22,7 +22,7 @@ if [ "$MODE" = all ] || [ "$MODE" = tests ]; then
   step smoke 300 python __graft_entry__.py smoke
 fi
 if [ "$MODE" = all ] || [ "$MODE" = bench ]; then
-  step bench 900 python bench.py ${BENCH_ARGS}
+  step bench 900 python bench.py --full ${BENCH_ARGS}
 fi
 tail -5 gpurun_out/pytest_gpu.log 2>/dev/null; tail -3 gpurun_out/smoke.log 2>/dev/null; tail -2 gpurun_out/bench.log 2>/dev/null
 cat gpurun_out/steps.log
