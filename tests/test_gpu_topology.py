@@ -8,6 +8,8 @@ unstable sort; fem355 puts the lower (element, face) first); normals 1e-14 relat
 normals_and_area function raises inside the reference (`:2409`): its intended result is checked against the
 oracle's restatement only (parity unpinned). Full size: the 10M-tet cube's face / edge counts satisfy the closed
 forms (12 n^2 boundary triangles, Euler characteristic 1) and sampled pairs really share their nodes.
+Every mesh here has one-word face keys (3 * 21 bits at most) and manifold faces; two-word keys, the key-width
+boundaries, ids >= 2^32, faces of multiplicity 3 and 4 and medium hex / wedge meshes: `tests/test_gpu_topology_keys.py`.
 """
 import pytest
 import torch
