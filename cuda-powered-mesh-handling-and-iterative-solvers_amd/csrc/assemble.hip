@@ -27,13 +27,18 @@ __global__ void __launch_bounds__(256) k_tet4_ke(const double* __restrict__ X, c
     if (threadIdx.x < 64) {
         int64_t e = e0 + threadIdx.x;
         if (e < M) {
-            double g[4][3];
-            double det = tet4_grads(X, conn + 4 * e, g);
+            double det;
+            if (KIND == FEM_KIND_MASS) {   // only V enters: the same bits for any local order of the element's nodes
+                det = tet4_det_sorted(X, conn + 4 * e);
+            } else {
+                double g[4][3];
+                det = tet4_grads(X, conn + 4 * e, g);
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) g_s[threadIdx.x][a][k] = g[a][k];
+            }
             if (fabs(det) < 1e-12) atomicMin((unsigned long long*)bad, (unsigned long long)e);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) g_s[threadIdx.x][a][k] = g[a][k];
             v_s[threadIdx.x] = fabs(det) / 6.0;
         }
     }

@@ -57,6 +57,31 @@ __device__ __forceinline__ double tet4_grads(const double* __restrict__ X, const
     return tet4_grads_n(X, n, g);
 }
 
+// signed det of the edge matrix with the 4 nodes taken in ascending global id. |det| is a symmetric function of the
+// nodes; formed from the local order it rounds differently in the last bit when an element is renumbered (other
+// edges are differenced). Sorted, any local order of the same nodes gives the same |det| bit for bit (the c3d4 mass).
+__device__ __forceinline__ double tet4_det_sorted(const double* __restrict__ X, const int64_t* __restrict__ c) {
+    int64_t n[4] = {c[0], c[1], c[2], c[3]};
+#define FEM_CSWAP(i, j)                \
+    if (n[j] < n[i]) {                 \
+        const int64_t t_ = n[i];       \
+        n[i] = n[j];                   \
+        n[j] = t_;                     \
+    }
+    FEM_CSWAP(0, 1) FEM_CSWAP(2, 3) FEM_CSWAP(0, 2) FEM_CSWAP(1, 3) FEM_CSWAP(1, 2)
+#undef FEM_CSWAP
+    double e1[3], e2[3], e3[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double p0 = X[3 * n[0] + k];
+        e1[k] = X[3 * n[1] + k] - p0;
+        e2[k] = X[3 * n[2] + k] - p0;
+        e3[k] = X[3 * n[3] + k] - p0;
+    }
+    return e1[0] * (e2[1] * e3[2] - e2[2] * e3[1]) + e1[1] * (e2[2] * e3[0] - e2[0] * e3[2]) +
+           e1[2] * (e2[0] * e3[1] - e2[1] * e3[0]);
+}
+
 // inverse of a row-major 3x3 Jacobian (cofactors), returns det
 __device__ __forceinline__ double inv3(const double J[9], double Ji[9]) {
     const double c00 = J[4] * J[8] - J[5] * J[7], c01 = J[5] * J[6] - J[3] * J[8], c02 = J[3] * J[7] - J[4] * J[6];
