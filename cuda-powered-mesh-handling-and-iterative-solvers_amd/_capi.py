@@ -162,7 +162,6 @@ SIGNATURES = {
     "fem_mf_apply": (_I, [_P, _P, _P, _P]),
     "fem_mf_diag": (_I, [_P, _P, _P]),
     "fem_mf_info": (_I, [_P, ctypes.POINTER(_L)]),
-    "fem_mf_spcheck": (_I, [_P]),
     "fem_mf_order": (_I, [_P, _P, _P, _P, _P, _P]),
     "fem_pcg_set_operator_mf": (_I, [_P, _P]),
     "fem_comm_unique_id": (_I, [ctypes.c_char_p]),

@@ -701,15 +701,9 @@ __device__ __forceinline__ RowWalk row_walk(int waves, int rows_per_wave = 1, in
 // thread-per-row kernel (bit-identical). Repeated nodes inside one element (degenerate input) take the exact
 // extra-bit loop.
 constexpr int AW_WAVES = 4;   // waves per 256-thread block of the wave-per-row assembly kernels
-#ifndef FEM_P1_LPR
-#define FEM_P1_LPR 16   // P1 assembly: lanes per row (four rows per wave; 64: 2.95 ms, 32: 1.52, 16: 1.11 on 10M tets)
-#endif
-#ifndef FEM_KE_KU
-#define FEM_KE_KU 8     // bs = 3 / bs = 1 assembly from K_e: incident elements whose loads are in flight per batch
-#endif
-#ifndef FEM_KE_RPL3
-#define FEM_KE_RPL3 1   // bs = 3 assembly from K_e: block rows per lane (3, one lane per column: c3d8 4.2 -> 5.1 ms)
-#endif
+constexpr int P1_LPR = 16;    // P1 assembly: lanes per row (four rows per wave; 64: 2.95 ms, 32: 1.52, 16: 1.11 on 10M tets)
+constexpr int KE_KU = 8;      // bs = 3 / bs = 1 assembly from K_e: incident elements whose loads are in flight per batch
+constexpr int KE_RPL3 = 1;    // bs = 3 assembly from K_e: block rows per lane (3, one lane per column: c3d8 4.2 -> 5.1 ms)
 
 // CSRW: the row sums (from zero) go to out in row-contiguous block-CSR order (block j of row i at
 // (rowptr[i] + j) BS^2, row-major) -- every wave writes a contiguous range -- and k_csr_add_sell adds them into the SELL
@@ -726,7 +720,7 @@ __global__ void __launch_bounds__(256) k_assemble_ke_w(const double* __restrict_
     constexpr int LPC = BS / RPL;
     constexpr int JG = 64 / LPC;
     constexpr int D = NPE * BS;
-    constexpr int KU = (RPL == 1) ? FEM_KE_KU : 4;
+    constexpr int KU = (RPL == 1) ? KE_KU : 4;
     __shared__ int node_s[AW_WAVES][64 * NPE];
     __shared__ int64_t krow_s[AW_WAVES][64];   // offset of the element's block row a in Ke
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -870,24 +864,14 @@ struct KeRowLane {
 // when one of the lanes (u, b2 < b) holds the same node. Cross-lane reads of the nodes the lanes already hold (NPE - 1
 // independent ds_bpermute, the whole wave active) instead of reloading the element's first b nodes from memory one
 // after the other (a loop of up to NPE - 1 dependent global loads per incidence pass). Lanes without an incidence
-// pass a distinct negative node (-1 - lane): never a match. FEM_KE_DUPLOAD = 1: the reload loop (A/B).
-#ifndef FEM_KE_DUPLOAD
-#define FEM_KE_DUPLOAD 0
-#endif
+// pass a distinct negative node (-1 - lane): never a match.
 // ke_row3 (bs = 3) takes the cross-lane check from 8 nodes per element on: c3d6's stiffness measured slower with it
 // (0.83 vs 0.66 ms; c3d10 1.87 vs 2.19, c3d8 1.67 vs 1.69; profiles/r06zg_dup_check_ab.txt); ke_row1 for every NPE
-// FEM_KE_ATOM1 = 1 (default): ke_row1's adds as LDS atomics (ds_add_f64, no return) -- one incidence per step, so the
-// lanes of a step hit distinct slots, and a wave's LDS operations complete in issue order: the same sums, bit for bit.
-// bs = 1 stored-matrix assembly 2-4 % faster (profiles/r06zg_dup_check_ab.txt); 0: read-modify-write
-#ifndef FEM_KE_ATOM1
-#define FEM_KE_ATOM1 1
-#endif
-// FEM_KE_PIPE1 = 1 (A/B): ke_row1's passes software-pipelined (loads one / two passes ahead); 0 (default): one pass at a time
-#ifndef FEM_KE_PIPE1
-#define FEM_KE_PIPE1 0
-#endif
+// ke_row1's adds are LDS atomics (ds_add_f64, no return) -- one incidence per step, so the lanes of a step hit distinct
+// slots, and a wave's LDS operations complete in issue order: the same sums as read-modify-write, bit for bit, and the
+// bs = 1 stored-matrix assembly 2-4 % faster (profiles/r06zg_dup_check_ab.txt). Its passes run one at a time.
 template <int NPE>
-constexpr bool ke_dup_shfl3() { return !FEM_KE_DUPLOAD && NPE >= 8; }
+constexpr bool ke_dup_shfl3() { return NPE >= 8; }
 template <int NPE>
 __device__ __forceinline__ int ke_dup_in_incidence(int node, int b, int lane) {
     int dup = 0;
@@ -899,19 +883,10 @@ __device__ __forceinline__ int ke_dup_in_incidence(int node, int b, int lane) {
     return dup;
 }
 
-// FEM_KE_ATOM = 1 (A/B; measured no faster, profiles/r06ze_ke_atom_fused_ab.txt): each add is one LDS add (ds_add_f64, no return) instead of a read, a wait and a write --
-// the lanes of one step hit distinct accumulators (distinct (b, r, c); distinct slots per b, or one b per step in the
-// repeated-node branch) and a wave's LDS operations complete in issue order, so every accumulator still sums in
-// ascending (incidence, b) order, bit for bit; 0 (default): the read-modify-write form
-#ifndef FEM_KE_ATOM
-#define FEM_KE_ATOM 0
-#endif
+// ke_row3's adds are a read, a wait and a write: one LDS add each (ds_add_f64, no return) measured no faster
+// (profiles/r06ze_ke_atom_fused_ab.txt)
 __device__ __forceinline__ void ke_lds_add(double* p, double v) {
-#if FEM_KE_ATOM
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
     *p += v;
-#endif
 }
 
 // MS: also the scalar element matrices Me [M, NPE, NPE] (e.g. the consistent-mass factor M_s of M = M_s (x) I3) of the
@@ -1168,67 +1143,6 @@ __device__ __forceinline__ void ke_row1(const double* __restrict__ Ke, const int
                                         double* acc, int lane) {
     constexpr int KU = 64 / NPE;
     const int u = lane / NPE, b = lane - NPE * (lane / NPE);
-#if FEM_KE_PIPE1
-    // software pipeline over the row's passes of KU incidences: the incidence entries two passes ahead and the node
-    // ids / values one pass ahead are in flight while a pass searches and adds. Every load is unconditional (indices
-    // clamped into the row; validity kept apart), so the waits stay partial; the same adds in the same order
-    if (C <= 0) return;
-    const auto ld_inc = [&](int kk) { return inc[t0 + min(kk + u, C - 1)]; };
-    int eaB = ld_inc(0);
-    int eaC = ld_inc(KU);
-    int nodeB, nodeC = 0;
-    double vB, vC = 0.0;
-    {
-        const int e = eaB / NPE;
-        nodeB = (int)conn[(int64_t)e * NPE + b];
-        vB = Ke[(int64_t)e * NPE * NPE + (eaB - e * NPE) * NPE + b];
-    }
-    for (int k0 = 0; k0 < C; k0 += KU) {
-        const int nu = min(KU, C - k0);
-        const int eaD = ld_inc(k0 + 2 * KU);
-        {
-            const int e = eaC / NPE;
-            nodeC = (int)conn[(int64_t)e * NPE + b];
-            vC = Ke[(int64_t)e * NPE * NPE + (eaC - e * NPE) * NPE + b];
-        }
-        const bool on = u < nu;
-        const int node = on ? nodeB : -1 - lane;
-        const double v = vB;
-        int s = -1;
-        if (on) {
-            int l = 0, h = nj;
-            while (l < h) {
-                const int mid = (l + h) >> 1;
-                if (cs[mid] < node) l = mid + 1;
-                else h = mid;
-            }
-            s = (l < nj && cs[l] == node) ? l : -1;
-        }
-        const int dup = ke_dup_in_incidence<NPE>(node, b, lane);
-        __builtin_amdgcn_wave_barrier();
-        if (!__any(dup)) {
-            for (int uu = 0; uu < nu; ++uu) {   // one incidence at a time: its NPE slots are distinct
-#if FEM_KE_ATOM1
-                if (u == uu && s >= 0) __hip_atomic_fetch_add(&acc[s], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-                if (u == uu && s >= 0) acc[s] += v;
-#endif
-                __builtin_amdgcn_wave_barrier();
-            }
-        } else {   // an element lists a node twice: its b's one after the other
-            for (int uu = 0; uu < nu; ++uu)
-                for (int bb = 0; bb < NPE; ++bb) {
-                    if (u == uu && b == bb && s >= 0) acc[s] += v;
-                    __builtin_amdgcn_wave_barrier();
-                }
-        }
-        eaC = eaD;
-        nodeB = nodeC;
-        vB = vC;
-    }
-    __builtin_amdgcn_wave_barrier();
-    return;
-#endif
     for (int k0 = 0; k0 < C; k0 += KU) {
         const int nu = min(KU, C - k0);
         double v = 0.0;
@@ -1246,21 +1160,12 @@ __device__ __forceinline__ void ke_row1(const double* __restrict__ Ke, const int
                 else h = mid;
             }
             s = (l < nj && cs[l] == node) ? l : -1;
-#if FEM_KE_DUPLOAD
-            for (int b2 = 0; b2 < b; ++b2) dup |= (int)conn[eb + b2] == node;
-#endif
         }
-#if !FEM_KE_DUPLOAD
         dup = ke_dup_in_incidence<NPE>(node, b, lane);
-#endif
         __builtin_amdgcn_wave_barrier();
         if (!__any(dup)) {
             for (int uu = 0; uu < nu; ++uu) {   // one incidence at a time: its NPE slots are distinct
-#if FEM_KE_ATOM1
                 if (u == uu && s >= 0) __hip_atomic_fetch_add(&acc[s], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-                if (u == uu && s >= 0) acc[s] += v;
-#endif
                 __builtin_amdgcn_wave_barrier();
             }
         } else {   // an element lists a node twice: its b's one after the other
@@ -1413,12 +1318,8 @@ __device__ __forceinline__ double el_combine(const Lame& L, double m_rc, double 
     return s;
 }
 
-#ifndef FEM_ACC_POSREP
-#define FEM_ACC_POSREP 0   // bs = 3: the repeated-node flag in the position fields (no a_s read; without the
-                           // atomics' per-step check, FEM_ACC_ATOM, nothing reads the flag)
-#endif
-// the accumulator kernel's column positions are 16-bit fields (bs = 3: 15-bit beside the flag), all-ones = absent
-constexpr int acc_max_cols(int bs) { return FEM_ACC_POSREP && bs == 3 ? 0x7fff : 0xffff; }
+// the accumulator kernel's column positions are 16-bit fields, all-ones = absent
+constexpr int ACC_MAX_COLS = 0xffff;
 
 // lane L of every quad (four consecutive lanes) to all four lanes of it (DPP quad_perm, no LDS)
 template <int L>
@@ -1435,22 +1336,9 @@ __device__ __forceinline__ double p1_value(const double ga[3], const double gb[3
     return kappa * dot * V;
 }
 
-// position of j in the ascending cs[0, n) (0xffff: absent): branch-free halving whose step count depends on n only
-// (rows of one wave share it), every read inside [0, n)
-__device__ __forceinline__ uint32_t sorted_pos(const int32_t* cs, int n, int j) {
-    if (n <= 0) return 0xffffu;
-    int b = 0;
-    for (int len = n; len > 1;) {
-        const int half = len >> 1;
-        b = cs[b + half] < j ? b + half : b;
-        len -= half;
-    }
-    b += cs[b] < j;
-    return (b < n && cs[b] == j) ? (uint32_t)b : 0xffffu;
-}
-
-// sorted_pos of four keys in one lockstep search (the same halving steps and result per key): the four probes of a
-// step are independent LDS reads in flight together instead of four searches one after another
+// positions p[q] of the four keys j[q] in the ascending cs[0, n) (0xffff: absent): branch-free halving whose step
+// count depends on n only (rows of one wave share it), every read inside [0, n). The four keys in one lockstep search:
+// the four probes of a step are independent LDS reads in flight together instead of four searches one after another
 __device__ __forceinline__ void sorted_pos4(const int32_t* cs, int n, const int j[4], uint32_t p[4]) {
     if (n <= 0) {
 #pragma unroll
@@ -1510,23 +1398,15 @@ struct AccCfg {
 // the tile's columns staged in LDS instead of the per-batch prefetch (XS): 3.0 ms at 8 items per row, 2.96 / 3.37 /
 // 3.12 ms at 5 / 6 / 4 -- the staging's gathers at the tile start are exposed, and 3 instead of 4 tiles per CU).
 // Round 6, the sweep's LDS operations per (row, item) step cut from 13 to 6 (profiles/r06o_acc_sweep_ab.txt,
-// r06r_acc_sweep_step2_ab.txt; 10M cube, bit-identical): the adds as LDS atomics (FEM_ACC_ATOM: 2277 -> 2248 us;
-// P1 649 -> 641 us), the P sum from the quad's products over DPP (FEM_ACC_PDPP), g_b read once per quad
-// (FEM_ACC_GDPP), and no per-step repeated-node check under the atomics: 1952 us; P1 618 us.
-#ifndef FEM_P1_CFG
-#define FEM_P1_CFG 64, 4, 4, 32, 1024
-#endif
-using AccP1 = AccCfg<FEM_P1_CFG>;
-#ifndef FEM_P1W16_CFG
-#define FEM_P1W16_CFG 64, 4, 4, 16, 1024
-#endif
+// r06r_acc_sweep_step2_ab.txt; 10M cube, bit-identical): the adds as LDS atomics (2277 -> 2248 us;
+// P1 649 -> 641 us), the P sum from the quad's products over DPP, g_b read once per quad, and no per-step
+// repeated-node check under the atomics: 1952 us; P1 618 us. Measured slower and not kept
+// (profiles/r06u_acc_negative_ab.txt): a hash table of the reference row's deltas for bs = 3, loads a whole phase ahead.
+using AccP1 = AccCfg<64, 4, 4, 32, 1024>;
 // patterns of at most 16 columns per row (10M cube: 0.67 vs 0.74 ms); with the coordinate prefetch (XP) 0.83 ms:
 // 107 VGPRs, 4 instead of 6 waves per SIMD
-using AccP1w16 = AccCfg<FEM_P1W16_CFG>;
-#ifndef FEM_EL3_CFG
-#define FEM_EL3_CFG 16, 8, 16, 16, 256, true, false
-#endif
-using AccEl = AccCfg<FEM_EL3_CFG>;
+using AccP1w16 = AccCfg<64, 4, 4, 16, 1024>;
+using AccEl = AccCfg<16, 8, 16, 16, 256, true, false>;
 
 // SL: the values go into the solver layout -- bs = 1 (whole-slice tiles): lane-paired entries of the pattern's
 // k_sell_sl_pattern, and in a slice-uniform slice (uoff[s] >= 0) the accumulators are indexed by the slice's delta
@@ -1558,67 +1438,23 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
     __shared__ int ip_s[R + 1];
     __shared__ int rp_s[R + 1];
     __shared__ int col_s[SEG];
-    // FEM_ASM_HASH (bs = 1, slice-uniform tiles): the slice's delta list also in a 64-slot open-addressing table
+    // bs = 1, slice-uniform tiles: the slice's delta list also in a 64-slot open-addressing table
     // (delta -> list position), so an element node's column is one LDS read (rarely two) instead of a binary search
-    // whose reads depend on each other. A timing build without any column search (FEM_ASM_NOSEARCH, wrong values)
-    // ran the 10M P1 value kernel in 544 instead of 724 us.
-#ifndef FEM_ASM_HASH
-#define FEM_ASM_HASH 1
-#endif
-#ifndef FEM_ASM_NOSEARCH
-#define FEM_ASM_NOSEARCH 0
-#endif
-#ifndef FEM_ASM_SEARCH4
-#define FEM_ASM_SEARCH4 1   // the other tiles: the four binary searches of an item in lockstep (sorted_pos4)
-#endif
-    constexpr bool HT = FEM_ASM_HASH && SL && BS == 1;
-    // FEM_ASM_HASH3 (bs = 3): the tile's longest row (the first of them) is the reference; its deltas (column - row)
-    // go into the same 64-slot table, and every row whose deltas equal them (all of a Kuhn cube's interior tiles)
-    // looks its element nodes' positions up there -- the same positions as the binary search, one LDS read each
-    // instead of ~5 dependent ones. Other rows keep the lockstep search.
-#ifndef FEM_ASM_HASH3
-#define FEM_ASM_HASH3 0   // measured slower (profiles/r06u_acc_negative_ab.txt): off
-#endif
-    constexpr bool HT3 = FEM_ASM_HASH3 && BS == 3;
+    // whose reads depend on each other. A timing build without any column search (wrong values)
+    // ran the 10M P1 value kernel in 544 instead of 724 us. The other tiles: the four binary searches of an item in
+    // lockstep (sorted_pos4).
+    constexpr bool HT = SL && BS == 1;
     constexpr int HTN = 64;
-    __shared__ int2 ht_s[(HT || HT3) ? HTN : 1];
-    __shared__ int hrow_s[HT3 ? R : 1];   // HT3: row r's deltas are the reference row's
+    __shared__ int2 ht_s[HT ? HTN : 1];
     __shared__ double xs_s[Cfg::XS ? SEG : 1][3];
     // padded strides: the sweep's lanes of one row read dat_s rows of different element nodes and update
     // accumulators of different columns -- with power-of-two strides those all fall into one LDS bank
     __shared__ double dat_s[ND][NI + 1];
     __shared__ uint2 pos_s[NI];
-    __shared__ uint8_t a_s[NI];             // local index of the row's node; bit 7: the element repeats a node
-    // accumulators of (column slot i = k AV + value, row r): [i][r] with a padded row stride (default), or
-    // FEM_ACC_T = 1 (bs = 3, A/B): [r][i] with row stride AW AV + FEM_ACC_PAD -- the sweep's 16 lanes of one row then
-    // hit consecutive slots of their columns, the 4 rows of a wave offset by the padded stride
-#ifndef FEM_ACC_T
-#define FEM_ACC_T 0
-#endif
-#ifndef FEM_ACC_PAD
-#define FEM_ACC_PAD 1
-#endif
-    // bs = 3: positions of 15 bits, the repeated-node flag in bit 15 of every field (no a_s read in the sweep)
-    constexpr bool POSREP = FEM_ACC_POSREP && BS == 3;
-#ifndef FEM_ACC_PROBE
-#define FEM_ACC_PROBE 0   // timing builds (wrong values): 1 no gradients, 2 no sweep, with FEM_ASM_NOSEARCH no search
-#endif
-#ifndef FEM_ACC_PF2
-#define FEM_ACC_PF2 0   // loads a whole phase ahead (measured slower, profiles/r06u_acc_negative_ab.txt)
-#endif
-#ifndef FEM_ACC_ATOM
-#define FEM_ACC_ATOM 1   // sweep adds as LDS atomics
-#endif
-#ifndef FEM_ACC_GDPP
-#define FEM_ACC_GDPP 1   // bs = 3 (with PDPP): g_b read once per quad and shared over DPP
-#endif
-#ifndef FEM_ACC_PDPP
-#define FEM_ACC_PDPP 1   // bs = 3: the P sum from the quad's products (DPP) instead of three more LDS reads
-#endif
-    constexpr bool ACT = FEM_ACC_T && BS == 3;
-    constexpr int ARS = ACT ? AW * AV + FEM_ACC_PAD : R + 1;   // stride of the outer index
-    __shared__ double acc_flat[ACT ? R * ARS : AW * AV * ARS];
-    auto ACC = [&](int i, int r) -> double& { return ACT ? acc_flat[r * ARS + i] : acc_flat[i * ARS + r]; };
+    // accumulators of (column slot i = k AV + value, row r): [i][r] with a padded row stride
+    constexpr int ARS = R + 1;
+    __shared__ double acc_flat[AW * AV * ARS];
+    auto ACC = [&](int i, int r) -> double& { return acc_flat[i * ARS + r]; };
     __shared__ int maxc_s;
     const int tid = threadIdx.x;
     const int64_t per = (ntiles + NXCD - 1) / NXCD;
@@ -1667,43 +1503,12 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                 xs_s[q][2] = X[3 * (int64_t)cq + 2];
             }
         }
-    bool use_ht3 = false;
-    if constexpr (HT3) {
-        int rref = 0, lref = rp_s[1] - rp_s[0];   // (every thread: the same reference row)
-        for (int r = 1; r < R; ++r) {
-            const int len = rp_s[r + 1] - rp_s[r];
-            if (len > lref) {
-                lref = len;
-                rref = r;
-            }
-        }
-        use_ht3 = staged && lref > 0 && lref <= HTN / 2;
-        if (use_ht3) {
-            for (int q = tid; q < HTN; q += NT) ht_s[q] = make_int2(INT_MIN, 0);
-            if (tid < R) hrow_s[tid] = (rp_s[tid + 1] - rp_s[tid]) == lref;
-            __syncthreads();   // col_s staged, table empty
-            const int cref = rp_s[rref] - seg0;
-            const int64_t gref = r0 + rref;
-            if (tid < lref) {
-                const int d = (int)(col_s[cref + tid] - gref);
-                unsigned h = ((unsigned)d * 2654435761u) >> 26;
-                while (atomicCAS(&ht_s[h].x, INT_MIN, d) != INT_MIN) h = (h + 1) & (HTN - 1);
-                ht_s[h].y = tid;
-            }
-            for (int q = tid; q < R * lref; q += NT) {   // a row of another delta list: back to the search
-                const int r = q / lref, k = q - r * lref;
-                if (hrow_s[r] && col_s[rp_s[r] - seg0 + k] - (r0 + r) != col_s[cref + k] - gref) hrow_s[r] = 0;
-            }
-        }
-    }
     const int maxc = maxc_s;
     const Lame L = lame(E, nu);
     // phase-2 lane: row lr, element node lb, block rows lrr .. lrr + RPL - 1
     const int lr = tid / LPR, lb = (BS == 1 || LPR == 4) ? tid % LPR : (tid % LPR) / 4;
     const int lrr = (BS == 1 || LPR == 4) ? 0 : tid % 4;   // bs = 3, LPR = 16: rr = 3 is the P lane
-    constexpr bool PDPP = FEM_ACC_PDPP && BS == 3 && LPR == 16;
-    constexpr bool REPCHK = !FEM_ACC_ATOM;
-    constexpr int ISTR = ACT ? 1 : ARS;   // accumulator stride between a column's consecutive slots
+    constexpr bool PDPP = BS == 3 && LPR == 16;
     // PDPP: the lane's first slot (block row lrr: 3 lrr, P lane: 9) and its accumulator address at column 0
     double* const abase = PDPP ? &ACC(lrr < 3 ? 3 * lrr : 9, lr) : nullptr;
     for (int c0 = 0; c0 < W; c0 += AW) {
@@ -1738,16 +1543,6 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                     for (int q = 0; q < 3; ++q) xn[b][q] = X[3 * cn_n[b] + q];
             }
         }
-        // PF2 (XP): incidence entries two batches ahead, node ids one batch ahead loaded as a batch starts (under
-        // its phase 1), coordinates one batch ahead as its sweep starts -- each load a whole phase before its use
-        constexpr bool PF2 = FEM_ACC_PF2 && Cfg::XP;
-        int ea_nn = 0;
-        bool v_nn = false;
-        if (PF2 && tid < NI && J < maxc) {
-            const int t = ip_s[ir] + J + ij;
-            v_nn = t < ip_s[ir + 1];
-            if (v_nn) ea_nn = inc[t];
-        }
         for (int j0 = 0; j0 < maxc; j0 += J) {
             __syncthreads();   // accumulators initialised / previous batch swept
             const bool vcur = v_n;
@@ -1760,32 +1555,16 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
 #pragma unroll
                     for (int q = 0; q < 3; ++q) xc[b][q] = xn[b][q];
             }
-            if constexpr (PF2) {
-                v_n = v_nn;
-                ea_n = ea_nn;
-                if (v_n) {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) cn_n[b] = conn[4 * (int64_t)(ea_n >> 2) + b];
-                }
-                v_nn = false;
-                if (tid < NI && j0 + 2 * J < maxc) {
-                    const int t = ip_s[ir] + j0 + 2 * J + ij;
-                    v_nn = t < ip_s[ir + 1];
-                    if (v_nn) ea_nn = inc[t];
-                }
-            } else {
-                v_n = false;
-                if (tid < NI && j0 + J < maxc) {
-                    const int t = ip_s[ir] + j0 + J + ij;
-                    v_n = t < ip_s[ir + 1];
-                    if (v_n) ea_n = inc[t];
-                }
+            v_n = false;
+            if (tid < NI && j0 + J < maxc) {
+                const int t = ip_s[ir] + j0 + J + ij;
+                v_n = t < ip_s[ir + 1];
+                if (v_n) ea_n = inc[t];
             }
             {
                 const int it0 = tid;
                 const int r = ir;
                 uint32_t pk[2] = {0xffffffffu, 0xffffffffu};
-                uint8_t aflag = 0;
                 if (tid < NI && vcur) {
                     const int ea = eacur;
                     const int64_t e = ea >> 2;
@@ -1794,43 +1573,21 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                     const bool ulist = SL && uo >= 0;
                     const int cl = ulist ? 0 : rp_s[r] - seg0, cn = ulist ? W : rp_s[r + 1] - rp_s[r];
                     const int kshift = ulist ? (int)(r0 + r) : 0;   // list entries are deltas node - row
-                    int nodes[4];
                     uint32_t pp[4];
                     pk[0] = pk[1] = 0u;
-                    // a table row: positions from the hash of the deltas node - row (hshift)
-                    const bool hrow = use_ht || (HT3 && use_ht3 && hrow_s[r]);
-                    const int hshift = use_ht ? kshift : (int)(r0 + r);
-#if !FEM_ASM_NOSEARCH
-                    int2 hfirst[4];   // HT3 table rows: the four keys' first probes, read together
-                    if (HT3 && hrow && !use_ht) {
-#pragma unroll
-                        for (int bb = 0; bb < 4; ++bb) {
-                            const int jd = (int)c[bb] - hshift;
-                            hfirst[bb] = ht_s[((unsigned)jd * 2654435761u) >> 26];
-                        }
-                    }
-                    if (!hrow && FEM_ASM_SEARCH4) {   // the four nodes' binary searches in lockstep
+                    if (!use_ht) {   // the four nodes' binary searches in lockstep
                         int jj4[4];
 #pragma unroll
                         for (int bb = 0; bb < 4; ++bb) jj4[bb] = (int)c[bb] - kshift;
                         if (staged) sorted_pos4(col_s + cl, cn, jj4, pp);
                         else sorted_pos4(colidx + seg0 + cl, cn, jj4, pp);
                     }
-#endif
 #pragma unroll
                     for (int bb = 0; bb < 4; ++bb) {
-                        nodes[bb] = (int)c[bb];
-                        const int j = nodes[bb] - kshift;
                         // the tile-uniform branch keeps the LDS search on ds_read (one pointer for both would
                         // make every probe a flat load)
-#if FEM_ASM_NOSEARCH   // timing builds only (wrong values): no column search, a fixed in-range slot
-                        pp[bb] = (uint32_t)(bb < cn ? bb : 0);
-                        (void)j;
-#else
-                        if (HT3 && hrow && !use_ht && hfirst[bb].x == nodes[bb] - hshift) {
-                            pp[bb] = (uint32_t)hfirst[bb].y;   // (the usual case: no collision on the first probe)
-                        } else if (hrow) {   // deltas are unique: the first matching key, or an empty slot = absent
-                            const int jd = nodes[bb] - hshift;
+                        if (use_ht) {   // deltas are unique: the first matching key, or an empty slot = absent
+                            const int jd = (int)c[bb] - kshift;
                             unsigned h = ((unsigned)jd * 2654435761u) >> 26;
                             uint32_t q = 0xffffu;
                             for (int probe = 0; probe < HTN; ++probe) {
@@ -1843,11 +1600,8 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                                 h = (h + 1) & (HTN - 1);
                             }
                             pp[bb] = q;
-                        } else if (!FEM_ASM_SEARCH4) {
-                            pp[bb] = staged ? sorted_pos(col_s + cl, cn, j) : sorted_pos(colidx + seg0 + cl, cn, j);
                         }
-#endif
-                        pk[bb >> 1] |= (POSREP ? pp[bb] & 0x7fffu : pp[bb]) << (16 * (bb & 1));
+                        pk[bb >> 1] |= pp[bb] << (16 * (bb & 1));
                     }
                     double g[4][3];
                     double det;
@@ -1863,15 +1617,7 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                             det = tet4_grads_n(X, cncur, g);
                         }
                     } else if constexpr (Cfg::XP) {
-#if FEM_ACC_PROBE & 1   // timing builds only (wrong values): no gradients (the coordinates stand in), det = 1
-                        det = 1.0;
-#pragma unroll
-                        for (int bb = 0; bb < 4; ++bb)
-#pragma unroll
-                            for (int q = 0; q < 3; ++q) g[bb][q] = xc[bb][q];
-#else
                         det = tet4_grads_p(xc, g);
-#endif
                     } else {
                         det = tet4_grads_n(X, cncur, g);
                     }
@@ -1880,11 +1626,6 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                     if constexpr (BS == 1) {
 #pragma unroll
                         for (int bb = 0; bb < 4; ++bb) dat_s[bb][it0] = p1_value(g[a], g[bb], E, V);
-                    }
-                    if constexpr (REPCHK || POSREP) {   // (nothing reads the flag otherwise)
-                        const bool rep = nodes[0] == nodes[1] || nodes[0] == nodes[2] || nodes[0] == nodes[3] ||
-                                         nodes[1] == nodes[2] || nodes[1] == nodes[3] || nodes[2] == nodes[3];
-                        aflag = (uint8_t)(a | (rep ? 0x80 : 0));
                     }
                     if constexpr (BS == 3) {
 #pragma unroll
@@ -1898,25 +1639,18 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                             for (int q = 0; q < 3; ++q) dat_s[3 + 3 * bb + q][it0] = g[bb][q];
                     }
                 }
-                if (tid < NI) {
-                    if (POSREP && (aflag & 0x80)) {   // bit 15 of every field: the element repeats a node
-                        pk[0] |= 0x80008000u;
-                        pk[1] |= 0x80008000u;
-                    }
-                    pos_s[it0] = make_uint2(pk[0], pk[1]);
-                    if constexpr (REPCHK) a_s[it0] = aflag;
-                }
+                if (tid < NI) pos_s[it0] = make_uint2(pk[0], pk[1]);
             }
             __syncthreads();
-            if (!PF2 && v_n) {   // the next batch's element node ids (its incidence entry was loaded above)
+            if (v_n) {   // the next batch's element node ids (its incidence entry was loaded above)
 #pragma unroll
                 for (int b = 0; b < 4; ++b) cn_n[b] = conn[4 * (int64_t)(ea_n >> 2) + b];
             }
             // sweep: lanes of one row are consecutive lanes of one wave, in lockstep
 #pragma unroll
-            for (int jj = 0; jj < ((FEM_ACC_PROBE & 2) ? 0 : J); ++jj) {   // (probe 2: no sweep, timing only)
+            for (int jj = 0; jj < J; ++jj) {
                 if constexpr (Cfg::XP) {
-                    if (jj == (PF2 ? 0 : J / 2) && v_n) {   // the next batch's coordinates, under the sweep
+                    if (jj == J / 2 && v_n) {   // the next batch's coordinates, under the sweep
 #pragma unroll
                         for (int b = 0; b < 4; ++b)
 #pragma unroll
@@ -1926,11 +1660,8 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                 const int it = lr * J + jj;
                 const uint2 pp = pos_s[it];
                 const uint32_t fld = ((lb < 2 ? pp.x : pp.y) >> (16 * (lb & 1))) & 0xffffu;
-                constexpr uint32_t NOPOS = POSREP ? 0x7fffu : 0xffffu;
-                const uint32_t praw = fld & NOPOS;
-                const int k = (int)praw - c0;
-                const bool hit = praw != NOPOS && k >= 0 && k < cw;
-                const uint8_t af = POSREP ? (uint8_t)((fld >> 15) << 7) : a_s[it];
+                const int k = (int)fld - c0;
+                const bool hit = fld != 0xffffu && k >= 0 && k < cw;
                 // bs = 3: NV products M[r][c] = (V g_a[r]) g_b[c] of the lane's block rows, then (P lane / LPR = 4)
                 // P = (V g_a) . g_b; every value lands in its own accumulator slot of column k
                 constexpr int NV = BS == 1 ? 1 : (LPR == 4 ? 10 : 3);
@@ -1942,12 +1673,8 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                     // the P lane takes the three products (V g_a[q]) g_b[q] it needs from lanes q = 0, 1, 2 of its
                     // quad (DPP broadcasts) -- el_pdot's rounded products summed in its order, without its three
                     // LDS reads. Unconditional (every lane active for the DPP); the values of a miss are not used.
-#if FEM_ACC_GDPP   // lane rr < 3 of the quad reads g_b[rr] alone, the quad shares the three over DPP
                     const double gmine = dat_s[3 + 3 * lb + (lrr < 3 ? lrr : 2)][it];
                     const double gb[3] = {quad_bcast<0>(gmine), quad_bcast<1>(gmine), quad_bcast<2>(gmine)};
-#else
-                    const double gb[3] = {dat_s[3 + 3 * lb][it], dat_s[4 + 3 * lb][it], dat_s[5 + 3 * lb][it]};
-#endif
                     const double vr = dat_s[lrr < 3 ? lrr : 2][it];
 #pragma unroll
                     for (int cc = 0; cc < 3; ++cc) v[cc] = vr * gb[cc];
@@ -1983,42 +1710,21 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                         }
                     }
                 }
-                // REPCHK (plain read-modify-writes): an element repeating a node would give two lanes of one step
-                // the same accumulator, so such a step goes node by node. With LDS atomics both adds land, and such an
-                // element has a determinant of exactly 0 (two equal columns, or a zero one): it is reported by `bad`
-                // (check_singular raises) and its NaN / inf values are never a result -- no per-step check.
-                const bool any_rep = REPCHK && __ballot(hit && (af & 0x80)) != 0;
-                if (!any_rep) {
-                    if (hit) {
+                // An element repeating a node gives two lanes of one step the same accumulator: with LDS atomics both
+                // adds land, and such an element has a determinant of exactly 0 (two equal columns, or a zero one): it
+                // is reported by `bad` (check_singular raises) and its NaN / inf values are never a result -- no
+                // per-step check.
+                if (hit) {
 #pragma unroll
-                        for (int cc = 0; cc < NV; ++cc) {
-                            if (cc < nv) {
-                                // PDPP: the lane's slot base is loop-invariant (abase), one multiply per address
-                                double* ap = PDPP ? abase + (k * AV + cc) * ISTR : &ACC(k * AV + slot0 + cc, lr);
-#if FEM_ACC_ATOM
-                                // one LDS add (ds_add_f64, no return) instead of a read, a wait and a write: the
-                                // row's lanes of one step hit distinct slots and a wave's LDS operations complete
-                                // in issue order, so every slot still sums in ascending incidence order
-                                __hip_atomic_fetch_add(ap, v[cc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-                                *ap = add_nc(*ap, v[cc]);
-#endif
-                            }
+                    for (int cc = 0; cc < NV; ++cc) {
+                        if (cc < nv) {
+                            // PDPP: the lane's slot base is loop-invariant (abase), one multiply per address
+                            double* ap = PDPP ? abase + (k * AV + cc) * ARS : &ACC(k * AV + slot0 + cc, lr);
+                            // one LDS add (ds_add_f64, no return) instead of a read, a wait and a write: the
+                            // row's lanes of one step hit distinct slots and a wave's LDS operations complete
+                            // in issue order, so every slot still sums in ascending incidence order
+                            __hip_atomic_fetch_add(ap, v[cc], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                         }
-                    }
-                } else {   // an element repeating a node: its nodes' contributions one after the other (b order)
-                    for (int b = 0; b < 4; ++b) {
-                        if (hit && lb == b) {
-#pragma unroll
-                            for (int cc = 0; cc < NV; ++cc) {
-                                if (cc < nv) {
-                                    double* ap = &ACC(k * AV + slot0 + cc, lr);
-                                    *ap = add_nc(*ap, v[cc]);
-                                }
-                            }
-                        }
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                     }
                 }
             }
@@ -2664,10 +2370,7 @@ static int assemble_from_ke(const double* Ke, const int64_t* conn, int npe, int 
                        getenv("FEM355_KE_ROWS") == nullptr;
     if (tile1) {
         const int Wc = max_width < KR_LMAX ? max_width : KR_LMAX;
-#ifndef FEM_KE_R1
-#define FEM_KE_R1 16
-#endif
-        constexpr int R1 = FEM_KE_R1;   // rows per tile (FEM_KE_R1: A/B of the tile height)
+        constexpr int R1 = 16;   // rows per tile
         const size_t dyn = sizeof(double) * (size_t)R1 * (Wc + 1);
         const int64_t ntiles = cdiv(N, 64) * (64 / R1);
         const dim3 g((unsigned)(cdiv(cdiv(N, 64), NXCD) * NXCD * (64 / R1)));
@@ -2722,7 +2425,7 @@ static int assemble_from_ke(const double* Ke, const int64_t* conn, int npe, int 
             FEM_HIP(::fem::malloc_async((void**)&tmp, sizeof(double) * 9 * (size_t)(nnz > 0 ? nnz : 1), S(stream)));
 #define FEM_KE_C(P)                                                                                             \
     if (npe == P && colform)                                                                                    \
-        hipLaunchKernelGGL((k_assemble_ke_w<3, P, FEM_KE_RPL3, true>), g, dim3(256), 0, S(stream), Ke, conn,     \
+        hipLaunchKernelGGL((k_assemble_ke_w<3, P, KE_RPL3, true>), g, dim3(256), 0, S(stream), Ke, conn,         \
                            inc_ptr, inc, N, rowptr, colidx, csr2sell, tmp);                                     \
     else if (npe == P)                                                                                          \
         hipLaunchKernelGGL(k_assemble_ke_rows3<P>, g, dim3(256), 0, S(stream), Ke, conn, inc_ptr, inc, N,       \
@@ -2743,7 +2446,7 @@ static int assemble_from_ke(const double* Ke, const int64_t* conn, int npe, int 
         }
 #define FEM_KE_W(B, P)                                                                                          \
     if (bs == B && npe == P)                                                                                    \
-        hipLaunchKernelGGL((k_assemble_ke_w<B, P, (B == 3 ? FEM_KE_RPL3 : 1)>), g, dim3(256), 0, S(stream), Ke,  \
+        hipLaunchKernelGGL((k_assemble_ke_w<B, P, (B == 3 ? KE_RPL3 : 1)>), g, dim3(256), 0, S(stream), Ke,      \
                            conn, inc_ptr, inc, N, rowptr, colidx, csr2sell, vals);
         FEM_KE_W(1, 4) FEM_KE_W(1, 6) FEM_KE_W(1, 8) FEM_KE_W(1, 10)
         FEM_KE_W(3, 4) FEM_KE_W(3, 6) FEM_KE_W(3, 8) FEM_KE_W(3, 10)
@@ -2773,9 +2476,9 @@ int fem_assemble_tet4_ex2(const double* coords, const int64_t* conn, double E, d
         return FEM_EARG;
     }
     if (N <= 0) return FEM_OK;
-    if (max_width >= acc_max_cols(bs)) {
+    if (max_width >= ACC_MAX_COLS) {
         set_error("fem_assemble_tet4: a row of %d columns exceeds the value kernel's %d", max_width,
-                  acc_max_cols(bs) - 1);
+                  ACC_MAX_COLS - 1);
         return FEM_EARG;
     }
     hipStream_t st = S(stream);
@@ -2792,7 +2495,7 @@ int fem_assemble_tet4_ex2(const double* coords, const int64_t* conn, double E, d
         }
         const dim3 g((unsigned)grid_multiple_of_xcd(cdiv(N, AW_WAVES), 8192));
         if (bs == 1)
-            hipLaunchKernelGGL(k_assemble_p1w<FEM_P1_LPR>, g, dim3(256), 0, st, coords, conn, E, inc_ptr, inc, N, rowptr, colidx, csr2sell, vals, bad_idx);
+            hipLaunchKernelGGL(k_assemble_p1w<P1_LPR>, g, dim3(256), 0, st, coords, conn, E, inc_ptr, inc, N, rowptr, colidx, csr2sell, vals, bad_idx);
         else
             hipLaunchKernelGGL(k_assemble_el3w, g, dim3(256), 0, st, coords, conn, E, nu, inc_ptr, inc, N, rowptr, colidx, csr2sell, vals, bad_idx);
         FEM_LAUNCHED();
@@ -2836,9 +2539,9 @@ int fem_assemble_tet4_sl(const double* coords, const int64_t* conn, double E, do
         set_error("fem_assemble_tet4_sl: block size %d unsupported", bs);
         return FEM_EARG;
     }
-    if (max_width >= acc_max_cols(bs)) {
+    if (max_width >= ACC_MAX_COLS) {
         set_error("fem_assemble_tet4_sl: a row of %d columns exceeds the value kernel's %d", max_width,
-                  acc_max_cols(bs) - 1);
+                  ACC_MAX_COLS - 1);
         return FEM_EARG;
     }
     hipStream_t st = S(stream);

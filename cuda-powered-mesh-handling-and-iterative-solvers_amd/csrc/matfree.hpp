@@ -18,85 +18,28 @@
 
 namespace fem {
 
-// slot stores (FEM_MF_NT = 1: non-temporal, the merged update reads them once after the kernel boundary)
-#ifndef FEM_MF_NT
-#define FEM_MF_NT 0
-#endif
+// slot stores: plain (non-temporal stores measured slower, the merged update reads the slots partly from L2 / MALL:
+// DESIGN §8g, profiles/r04f_mf_nontemporal_ab.log)
 __device__ __forceinline__ void mf_store_slot(double* p, double v) {
-#if FEM_MF_NT
-    __builtin_nontemporal_store(v, p);
-#else
     *p = v;
-#endif
 }
 
-
-// Chunk geometry. FEM_MF_WAVE (default): a chunk per WAVE -- <= 64 elements / <= 64 nodes (pieces of 16 elements when
-// more), every wave of a workgroup walking its own chunks with no workgroup barrier, ~10 KB of LDS per wave. Else a
-// chunk per workgroup: <= 512 elements / <= 256 nodes (pieces of 64), two passes of 256 elements, 41.6 KB per
-// workgroup and its barriers.
-#ifndef FEM_MF_WAVE
-#define FEM_MF_WAVE 0
-#endif
-#if FEM_MF_WAVE
-constexpr int MF_EC = 64;       // elements per chunk (at most)
-constexpr int MF_NC = 64;       // local nodes per chunk (at most)
-constexpr int MF_PIECE = 16;    // elements per piece of a chunk that touched more than MF_NC nodes
-#else
+// Chunk geometry: a chunk per workgroup -- <= 512 elements / <= 240 nodes (pieces of 32 elements when more), two passes
+// of 256 elements. (A chunk per wave, <= 64 elements / <= 64 nodes with no workgroup barrier, was the round-4 form.)
 // 240 nodes (not 256): with the pair pointers in registers and the element vectors unpadded the chunk's LDS is
 // 40,192 bytes, so 4 workgroups (16 waves) share a CU instead of 3 (41.6 KB each)
 constexpr int MF_EC = 512;
 constexpr int MF_NC = 240;      // local ids are bytes
 constexpr int MF_PIECE = 32;
-#endif
 static_assert(4 * MF_PIECE <= MF_NC, "a piece of MF_PIECE elements always fits the node cap");
-// FEM_MF_W512 = 1 (A/B): 512-thread workgroups -- the chunk's 512 element vectors formed in one pass (64 KB of LDS,
-// 2 workgroups per CU: the same 16 waves) and two lanes per local node in the node sums (each sums half of the
-// node's pairs in order, the halves added once: a node's sum no longer waits for its longest-walking neighbour lane)
-#ifndef FEM_MF_W512
-#define FEM_MF_W512 0
-#endif
-#if FEM_MF_W512 && !FEM_MF_WAVE
-constexpr int MF_PASS = 512;
-constexpr int MF_BLOCK = 512;
-constexpr int MF_LPN = 2;       // lanes per local node
-#else
-constexpr int MF_PASS = 256;    // elements formed per pass (= threads of the workgroup; workgroup chunks)
+constexpr int MF_PASS = 256;    // elements formed per pass (= threads of the workgroup)
 constexpr int MF_BLOCK = 256;
-constexpr int MF_LPN = 1;
-#endif
-#ifndef FEM_MF_UNROLL
-#define FEM_MF_UNROLL 4
-#endif
-constexpr int MF_U = FEM_MF_UNROLL;   // pairs whose LDS reads are issued together in the node sums
-// FEM_MF_F0 = 1: corner 0's element vector not staged, f_0 = -(f_1 + f_2 + f_3) (mf_element's own formula) re-formed by
-// the node sums that need it -- 3 of 4 vectors in LDS, 4 instead of 3 workgroups per CU for bs = 3; measured slower
-// (10M elastic chunk kernel 326 vs 231 us: the corner-0 branch diverges inside every wave's node sums), off
-#ifndef FEM_MF_F0
-#define FEM_MF_F0 0
-#endif
+constexpr int MF_U = 4;         // pairs whose LDS reads are issued together in the node sums
+// All four corners' element vectors are staged. Re-forming corner 0's as -(f_1 + f_2 + f_3) in the node sums (3 of 4
+// vectors in LDS, 4 instead of 3 workgroups per CU for bs = 3) measured slower: 10M elastic chunk kernel 326 vs 231 us,
+// the corner-0 branch diverges inside every wave's node sums.
 
 enum { MF_APPLY = 0, MF_DOT = 1, MF_DIAG = 2 };
-
-// FEM_MF_SPCHECK = 1 (debug build, tools/mf_spcheck.py; never the default): the slot position ALSO carried through
-// the prefetch records, as the walk did before commit c83e619, and compared at every slot store with the position
-// read under the chunk's work. mf_spcheck: [0] stores checked, [1] mismatches, [2] first mismatch (chunk << 16 | tid),
-// [3] its carried value, [4] the expected one, [5] its walk step (0 = first chunk of the workgroup)
-#ifndef FEM_MF_SPCHECK
-#define FEM_MF_SPCHECK 0
-#endif
-#if FEM_MF_SPCHECK
-__device__ unsigned long long mf_spcheck[8];
-#endif
-// FEM_MF_PROF (timing builds only, wrong results): bit 0 skips the element formation (the staged vectors are the
-// nodes' x), bit 1 the node sums (each slot gets one pair value) -- what the chunk kernel costs without each phase
-#ifndef FEM_MF_PROF
-#define FEM_MF_PROF 0
-#endif
-
-// staged corners of a mode (the diagonal's corner-0 values are not -(f_1 + f_2 + f_3))
-template <int MODE>
-constexpr int mf_fc() { return (FEM_MF_F0 && MODE != MF_DIAG) ? 3 : 4; }
 
 // device view of the operator
 struct MfOp {
@@ -218,72 +161,31 @@ __device__ __forceinline__ void mf_element(const double xc[4][3], const double x
     }
 }
 
-// FEM_MF_ELC = 1 (A/B): the element vectors of a pass staged [element][corner][component] (one
-// element's 4 BS values contiguous: its thread stores them as 16-byte writes, a node's pair read is one 16-byte and
-// one 8-byte LDS read for BS = 3 instead of three 8-byte reads 2 KB apart). Measured slower on the 10M elastic cube:
-// chunk kernel 220.4 / 221.3 vs 195.9 / 196.9 us (profiles/r06f_mf_elc_ab.txt): the select between the two read
-// shapes costs VALU and the 16-byte reads at 24-byte strides conflict more; 0 (default): [corner * BS + c][element].
-#ifndef FEM_MF_ELC
-#define FEM_MF_ELC 0
-#endif
-template <int FC>
-constexpr bool mf_elc() { return FEM_MF_ELC && FC == 4; }
-
 // LDS of one chunk application (a local node's pair range [lp, lp1) travels in its thread's registers)
-// FEM_MF_NDSKEW = 1 (A/B): the local-node rows of nd skewed by one 16-byte unit every 16 rows (a row is 3 (BS = 3) or
-// 2 (BS = 1) 16-byte units, so rows l and l + 16 start in the same 16-byte bank group). Measured slower on the 10M
-// elastic cube: chunk kernel 185-186 vs 179-180 us (profiles/r06h_mf_ndskew_ab.txt); off
-#ifndef FEM_MF_NDSKEW
-#define FEM_MF_NDSKEW 0
-#endif
-template <int BS, int FC>
+// Tried and measured slower on the 10M elastic cube: the element vectors staged [element][corner][component] (chunk
+// kernel 220.4 / 221.3 vs 195.9 / 196.9 us, profiles/r06f_mf_elc_ab.txt) and the node rows skewed by one 16-byte unit
+// every 16 rows (185-186 vs 179-180 us, profiles/r06h_mf_ndskew_ab.txt).
+template <int BS>
 struct MfLds {
     static constexpr int NDU = (3 + BS) / 2;   // 16-byte units per node row
-    // per local node: coordinates, then x (rows of NDU 16-byte units; row l at unit l NDU (+ l / 16 skewed))
-    double2 ndu[MF_NC * NDU + (FEM_MF_NDSKEW ? MF_NC / 16 + 1 : 0)];
-    __device__ __forceinline__ double2* nd_row(int l) { return ndu + l * NDU + (FEM_MF_NDSKEW ? (l >> 4) : 0); }
-    __device__ __forceinline__ const double2* nd_row(int l) const {
-        return ndu + l * NDU + (FEM_MF_NDSKEW ? (l >> 4) : 0);
-    }
-    // element vectors of the current pass: [staged corner * BS + c][element], or (mf_elc) fe[element][corner][c].
-    // Row stride MF_PASS + FEM_MF_FSPAD (default 1): the node sums' lanes read the corners of SHARED elements in the
+    // per local node: coordinates, then x (rows of NDU 16-byte units; row l at unit l NDU)
+    double2 ndu[MF_NC * NDU];
+    __device__ __forceinline__ double2* nd_row(int l) { return ndu + l * NDU; }
+    __device__ __forceinline__ const double2* nd_row(int l) const { return ndu + l * NDU; }
+    // element vectors of the current pass: [corner * BS + c][element].
+    // Row stride MF_PASS + 1: the node sums' lanes read the corners of SHARED elements in the
     // same step -- same element, rows 3 apart -- which a stride of 256 doubles (= 0 mod the 32 eight-byte bank pairs)
     // put into one bank; an odd stride spreads them
-#ifndef FEM_MF_FSPAD
-#define FEM_MF_FSPAD 1
-#endif
-    alignas(16) double fs[FC * BS][MF_PASS + FEM_MF_FSPAD];
+    alignas(16) double fs[4 * BS][MF_PASS + 1];
     alignas(16) uint16_t ent[4 * MF_EC];   // the chunk's pairs, node-major
 };
 
 // the element vector of pair pe (element << 2 | corner) of the pass starting at element h
-template <int BS, int FC>
-__device__ __forceinline__ void mf_pair_value(const MfLds<BS, FC>& L, int pe, int h, double v[BS]) {
+template <int BS>
+__device__ __forceinline__ void mf_pair_value(const MfLds<BS>& L, int pe, int h, double v[BS]) {
     const int el = (pe >> 2) - h, b = pe & 3;
-    if constexpr (mf_elc<FC>()) {
-        const double* fe = &L.fs[0][0];
-        const int base = (el * 4 + b) * BS;
-        if constexpr (BS == 3) {   // 24 bytes at 8 (mod 16) when b is odd: the 16-byte read one double later
-            const int odd = b & 1;
-            const double2 d = *reinterpret_cast<const double2*>(fe + base + odd);
-            const double sgl = fe[base + (odd ? 0 : 2)];
-            v[0] = odd ? sgl : d.x;
-            v[1] = odd ? d.x : d.y;
-            v[2] = odd ? d.y : sgl;
-        } else {
 #pragma unroll
-            for (int q = 0; q < BS; ++q) v[q] = fe[base + q];
-        }
-        return;
-    }
-    if (FC == 3 && b == 0) {
-#pragma unroll
-        for (int q = 0; q < BS; ++q) v[q] = -(L.fs[q][el] + L.fs[BS + q][el] + L.fs[2 * BS + q][el]);
-    } else {
-        const int row = (b - (4 - FC)) * BS;
-#pragma unroll
-        for (int q = 0; q < BS; ++q) v[q] = L.fs[row + q][el];
-    }
+    for (int q = 0; q < BS; ++q) v[q] = L.fs[b * BS + q][el];
 }
 
 // What a thread loads for one chunk ahead of its use (software pipeline over a workgroup's chunks): the chunk's
@@ -296,7 +198,7 @@ __device__ __forceinline__ void mf_pair_value(const MfLds<BS, FC>& L, int pe, in
 // makes the compiler wait for the loads in flight into it, and a load under a branch makes its wait counts
 // conservative past the branch (s_waitcnt vmcnt(0)): the round-4/5 walk, whose records were copied (cur = n1; n1 =
 // n2) and loaded under `tid < nn`, waited for each prefetch right after issuing it -- ~4 exposed memory latencies per
-// chunk (a FEM_MF_PROF = 3 build, no element formation and no node sums, still took 125 of the kernel's 217 us).
+// chunk (a timing build with no element formation and no node sums, still took 125 of the kernel's 217 us).
 // Every field is defined in every lane (copying indeterminate values was the round-4 NaN).
 typedef unsigned int mf_u32x4 __attribute__((ext_vector_type(4)));   // a native vector (HIP's uint4 is a union
                                                                         // wrapper that kept the records in scratch)
@@ -328,8 +230,7 @@ __device__ __forceinline__ void mf_pf1(const MfOp& op, int64_t c, MfPf<BS>& f) {
     f.ne = __builtin_amdgcn_readlane(f.b_e, 1) - f.e0;
     f.s0 = __builtin_amdgcn_readlane(f.b_s, 0);
     f.nn = __builtin_amdgcn_readlane(f.b_s, 1) - f.s0;
-    const int tn = tid / MF_LPN;                  // this lane's local node (MF_LPN lanes per node)
-    const int t = tn < f.nn ? tn : f.nn - 1;      // a chunk has >= 1 node and >= 1 element
+    const int t = tid < f.nn ? tid : f.nn - 1;    // this lane's local node (a chunk has >= 1 node and >= 1 element)
     f.node = op.cnode[f.s0 + t];
     f.lp = op.lptr[f.s0 + c + t];
     f.lp1 = op.lptr[f.s0 + c + t + 1];           // the chunk's end marker for its last node
@@ -357,16 +258,15 @@ __device__ __forceinline__ void mf_pf2(const MfOp& op, const double* __restrict_
 // pairs / local ids, cur its ranges for three chunks on. Returns whether this workgroup has a next chunk.
 template <int BS, int MODE>
 __device__ __forceinline__ bool mf_step(const MfOp& op, const double* __restrict__ x, double* __restrict__ slots,
-                                        MfLds<BS, mf_fc<MODE>()>& L, int64_t base, int64_t per, int64_t nb,
+                                        MfLds<BS>& L, int64_t base, int64_t per, int64_t nb,
                                         int64_t last, int64_t& k, MfPf<BS>& cur, MfPf<BS>& n1, MfPf<BS>& n2,
                                         double& dot) {
-    constexpr int FC = mf_fc<MODE>();
     const int tid = threadIdx.x;
     // chunks past this workgroup's range load its last chunk's data again (in range and in L2, never used)
     const auto chunk = [&](int64_t kk) { return kk < per && base + kk < op.nchunks ? base + kk : last; };
     __syncthreads();   // the previous chunk's LDS reads are done
-    const int tn = tid / MF_LPN;                   // this lane's local node
-    const bool own = tn < cur.nn && tid % MF_LPN == 0;   // the lane that installs and stores the node
+    const int tn = tid;               // this lane's local node
+    const bool own = tn < cur.nn;     // it installs and stores the node
     if (own) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) reinterpret_cast<double*>(L.nd_row(tn))[q] = cur.xv[q];
@@ -385,11 +285,6 @@ __device__ __forceinline__ bool mf_step(const MfOp& op, const double* __restrict
     for (int q = 0; q < BS; ++q) acc[q] = 0.0;
     int pos = tn < cur.nn ? cur.lp : 0;
     int end = tn < cur.nn ? cur.lp1 : 0;
-    if constexpr (MF_LPN == 2) {   // lane 0 of the node: the first half of its pairs, lane 1 the rest
-        const int half = (end - pos + 1) >> 1;
-        if (tid & 1) pos += half;
-        else end = pos + half;
-    }
     // the node's pairs split at the pass boundary (pairs ascend by element): lower bound of 4 MF_PASS
     int mid = end;
     if (cur.ne > MF_PASS) {
@@ -429,50 +324,23 @@ __device__ __forceinline__ bool mf_step(const MfOp& op, const double* __restrict
                     xv[b][2] = a2.y;
                 }
             }
-#if FEM_MF_PROF & 1
+            mf_element<BS, MODE>(xc, xv, op.lam, op.mu, op.kappa, f);
 #pragma unroll
             for (int b = 0; b < 4; ++b)
 #pragma unroll
-                for (int q = 0; q < BS; ++q) f[b][q] = xv[b][q] + xc[b][q];
-#else
-            mf_element<BS, MODE>(xc, xv, op.lam, op.mu, op.kappa, f);
-#endif
-            if constexpr (mf_elc<FC>()) {   // the element's 4 BS values contiguous (16-byte stores)
-                double2* fe2 = reinterpret_cast<double2*>(&L.fs[0][0] + tid * 4 * BS);
-                double fl[4 * BS];
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-#pragma unroll
-                    for (int q = 0; q < BS; ++q) fl[b * BS + q] = f[b][q];
-#pragma unroll
-                for (int t = 0; t < 2 * BS; ++t) fe2[t] = make_double2(fl[2 * t], fl[2 * t + 1]);
-            } else {
-#pragma unroll
-                for (int b = 4 - FC; b < 4; ++b)
-#pragma unroll
-                    for (int q = 0; q < BS; ++q) L.fs[(b - (4 - FC)) * BS + q][tid] = f[b][q];
-            }
+                for (int q = 0; q < BS; ++q) L.fs[b * BS + q][tid] = f[b][q];
         }
         __syncthreads();
         // every local node adds its pairs of this pass in ascending (element, corner) order; the pair reads of
         // four steps are issued before their adds (independent LDS loads, one latency per four pairs)
         const int stop = j == 0 ? mid : end;
-#if FEM_MF_PROF & 2
-        if (pos < stop) {
-            double v[BS];
-            mf_pair_value<BS, FC>(L, L.ent[pos], h, v);
-#pragma unroll
-            for (int q = 0; q < BS; ++q) acc[q] += v[q];
-            pos = stop;
-        }
-#endif
         for (; pos + MF_U <= stop; pos += MF_U) {
             int pe[MF_U];
 #pragma unroll
             for (int u = 0; u < MF_U; ++u) pe[u] = L.ent[pos + u];
             double v[MF_U][BS];
 #pragma unroll
-            for (int u = 0; u < MF_U; ++u) mf_pair_value<BS, FC>(L, pe[u], h, v[u]);
+            for (int u = 0; u < MF_U; ++u) mf_pair_value<BS>(L, pe[u], h, v[u]);
 #pragma unroll
             for (int u = 0; u < MF_U; ++u)
 #pragma unroll
@@ -480,15 +348,11 @@ __device__ __forceinline__ bool mf_step(const MfOp& op, const double* __restrict
         }
         for (; pos < stop; ++pos) {
             double v[BS];
-            mf_pair_value<BS, FC>(L, L.ent[pos], h, v);
+            mf_pair_value<BS>(L, L.ent[pos], h, v);
 #pragma unroll
             for (int q = 0; q < BS; ++q) acc[q] += v[q];
         }
         __syncthreads();
-    }
-    if constexpr (MF_LPN == 2) {   // the halves added once (a + b == b + a: both lanes hold the same sum)
-#pragma unroll
-        for (int q = 0; q < BS; ++q) acc[q] += __shfl_xor(acc[q], 1, 64);
     }
     if (own) {
 #pragma unroll
@@ -496,17 +360,6 @@ __device__ __forceinline__ bool mf_step(const MfOp& op, const double* __restrict
             mf_store_slot(&slots[(int64_t)(op.spos ? cur.sp : cur.s0 + tn) * BS + q], acc[q]);
             if constexpr (MODE == MF_DOT) dot += cur.pv[q] * acc[q];
         }
-#if FEM_MF_SPCHECK
-        // the carried position against one read now (the round-4 question)
-        const int spc = op.spos ? op.spos[cur.s0 + tn] : cur.s0 + tn;
-        atomicAdd(&mf_spcheck[0], 1ull);
-        if (op.spos && cur.sp != spc && atomicAdd(&mf_spcheck[1], 1ull) == 0) {
-            mf_spcheck[2] = ((unsigned long long)(base + k) << 16) | (unsigned)tid;
-            mf_spcheck[3] = (unsigned)cur.sp;
-            mf_spcheck[4] = (unsigned)spc;
-            mf_spcheck[5] = 0;
-        }
-#endif
     }
     k += nb;
     return k < per && base + k < op.nchunks;
@@ -520,7 +373,7 @@ __device__ __forceinline__ bool mf_step(const MfOp& op, const double* __restrict
 // its chunks (0 elsewhere). x unused for MF_DIAG.
 template <int BS, int MODE>
 __device__ __forceinline__ double mf_walk(const MfOp& op, const double* __restrict__ x, double* __restrict__ slots,
-                                          MfLds<BS, mf_fc<MODE>()>& L) {
+                                          MfLds<BS>& L) {
     const int64_t per = (op.nchunks + NXCD - 1) / NXCD;
     const int64_t base = (int64_t)(blockIdx.x % NXCD) * per;
     const int64_t nb = gridDim.x / NXCD;
@@ -544,203 +397,6 @@ __device__ __forceinline__ double mf_walk(const MfOp& op, const double* __restri
         if (!mf_step<BS, MODE>(op, x, slots, L, base, per, nb, last, k, C, A, B, dot)) break;
     }
     return dot;
-}
-
-// LDS of one wave's chunk (FEM_MF_WAVE)
-template <int BS, int FC>
-struct MfLdsW {
-    double nd[MF_NC][3 + BS];
-    double fs[FC * BS][MF_EC + 1];
-    uint16_t lp[MF_NC + 1];
-    alignas(16) uint16_t ent[4 * MF_EC];
-};
-
-// LDS hand-off between the lanes of one wave: program order for the compiler (the hardware runs a wave's LDS
-// operations in order)
-__device__ __forceinline__ void mf_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-template <int BS>
-struct MfPfW {
-    int e0, ne, s0, nn;
-    int node;
-    uint16_t lp;
-    uint2 ent;
-    uint32_t el;
-    double xv[3], pv[BS];
-};
-
-template <int BS>
-__device__ __forceinline__ void mf_pfw1(const MfOp& op, int64_t c, MfPfW<BS>& f) {
-    const int lane = threadIdx.x & 63;
-    f.e0 = __builtin_amdgcn_readfirstlane(op.cptr[c]);
-    f.ne = __builtin_amdgcn_readfirstlane(op.cptr[c + 1]) - f.e0;
-    f.s0 = __builtin_amdgcn_readfirstlane(op.sbase[c]);
-    f.nn = __builtin_amdgcn_readfirstlane(op.sbase[c + 1]) - f.s0;
-    f.node = 0;
-    f.lp = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) f.xv[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < BS; ++k) f.pv[k] = 0.0;
-    if (lane < f.nn) {
-        f.node = op.cnode[f.s0 + lane];
-        f.lp = op.lptr[f.s0 + c + lane];
-    }
-    f.ent = make_uint2(0, 0);
-    if (4 * lane < 4 * f.ne) f.ent = reinterpret_cast<const uint2*>(op.lent + 4 * (int64_t)f.e0)[lane];
-    f.el = lane < f.ne ? op.eloc[f.e0 + lane] : 0u;
-}
-
-template <int BS, int MODE>
-__device__ __forceinline__ void mf_pfw2(const MfOp& op, const double* __restrict__ x, MfPfW<BS>& f) {
-    if ((int)(threadIdx.x & 63) < f.nn) {
-        const int64_t g = f.node;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) f.xv[k] = op.X[3 * g + k];
-#pragma unroll
-        for (int k = 0; k < BS; ++k) f.pv[k] = MODE == MF_DIAG ? 0.0 : x[BS * g + k];
-    }
-}
-
-// Every chunk of this WAVE (chunk ranges per XCD; consecutive chunks on one XCD at once), three chunks in flight as in
-// mf_walk; lane l < nn owns local node l, lane e < ne element e. No workgroup barrier: the waves of a workgroup only
-// share the CU.
-template <int BS, int MODE>
-__device__ __forceinline__ double mf_walk_w(const MfOp& op, const double* __restrict__ x, double* __restrict__ slots,
-                                            MfLdsW<BS, mf_fc<MODE>()>& L) {
-    constexpr int FC = mf_fc<MODE>();
-    const int lane = threadIdx.x & 63;
-    constexpr int WPB = MF_BLOCK / 64;
-    const int64_t per = (op.nchunks + NXCD - 1) / NXCD;
-    const int64_t base = (int64_t)(blockIdx.x % NXCD) * per;
-    const int64_t nb = (int64_t)(gridDim.x / NXCD) * WPB;
-    int64_t k = (int64_t)(blockIdx.x / NXCD) * WPB + (threadIdx.x >> 6);
-    double dot = 0.0;
-    if (k >= per || base + k >= op.nchunks) return dot;
-    MfPfW<BS> cur, n1, n2;
-    mf_pfw1<BS>(op, base + k, cur);
-    bool has1 = k + nb < per && base + k + nb < op.nchunks;
-    if (has1) mf_pfw1<BS>(op, base + k + nb, n1);
-    mf_pfw2<BS, MODE>(op, x, cur);
-    for (;;) {
-        mf_wave_sync();   // the previous chunk's LDS reads are done
-        if (lane < cur.nn) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) L.nd[lane][q] = cur.xv[q];
-#pragma unroll
-            for (int q = 0; q < BS; ++q) L.nd[lane][3 + q] = cur.pv[q];
-            L.lp[lane] = cur.lp;
-        }
-        if (lane == 0) L.lp[cur.nn] = (uint16_t)(4 * cur.ne);
-        if (lane < cur.ne) reinterpret_cast<uint2*>(L.ent)[lane] = cur.ent;
-        const int64_t k2 = k + 2 * nb;
-        const bool has2 = has1 && k2 < per && base + k2 < op.nchunks;
-        if (has1) mf_pfw2<BS, MODE>(op, x, n1);
-        if (has2) mf_pfw1<BS>(op, base + k2, n2);
-        int spc = 0;   // this lane's slot position (see mf_walk)
-        if (lane < cur.nn) spc = op.spos ? op.spos[cur.s0 + lane] : cur.s0 + lane;
-        mf_wave_sync();
-        if (lane < cur.ne) {
-            const uint32_t w = cur.el;
-            double xc[4][3], xv[4][BS], f[4][BS];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int l = (w >> (8 * b)) & 0xff;
-                const double2* r = reinterpret_cast<const double2*>(&L.nd[l][0]);
-                const double2 a0 = r[0], a1 = r[1];
-                xc[b][0] = a0.x;
-                xc[b][1] = a0.y;
-                xc[b][2] = a1.x;
-                if constexpr (BS == 1) {
-                    xv[b][0] = a1.y;
-                } else {
-                    const double2 a2 = r[2];
-                    xv[b][0] = a1.y;
-                    xv[b][1] = a2.x;
-                    xv[b][2] = a2.y;
-                }
-            }
-            mf_element<BS, MODE>(xc, xv, op.lam, op.mu, op.kappa, f);
-#pragma unroll
-            for (int b = 4 - FC; b < 4; ++b)
-#pragma unroll
-                for (int q = 0; q < BS; ++q) L.fs[(b - (4 - FC)) * BS + q][lane] = f[b][q];
-        }
-        mf_wave_sync();
-        if (lane < cur.nn) {
-            double acc[BS];
-#pragma unroll
-            for (int q = 0; q < BS; ++q) acc[q] = 0.0;
-            int pos = L.lp[lane];
-            const int end = L.lp[lane + 1];
-            for (; pos + MF_U <= end; pos += MF_U) {
-                int pe[MF_U];
-#pragma unroll
-                for (int u = 0; u < MF_U; ++u) pe[u] = L.ent[pos + u];
-                double v[MF_U][BS];
-#pragma unroll
-                for (int u = 0; u < MF_U; ++u) {
-                    const int el = pe[u] >> 2, b = pe[u] & 3;
-                    if (FC == 3 && b == 0) {
-#pragma unroll
-                        for (int q = 0; q < BS; ++q) v[u][q] = -(L.fs[q][el] + L.fs[BS + q][el] + L.fs[2 * BS + q][el]);
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < BS; ++q) v[u][q] = L.fs[(b - (4 - FC)) * BS + q][el];
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < MF_U; ++u)
-#pragma unroll
-                    for (int q = 0; q < BS; ++q) acc[q] += v[u][q];
-            }
-            for (; pos < end; ++pos) {
-                const int pe = L.ent[pos];
-                const int el = pe >> 2, b = pe & 3;
-#pragma unroll
-                for (int q = 0; q < BS; ++q) {
-                    const double v = (FC == 3 && b == 0)
-                                         ? -(L.fs[q][el] + L.fs[BS + q][el] + L.fs[2 * BS + q][el])
-                                         : L.fs[(b - (4 - FC)) * BS + q][el];
-                    acc[q] += v;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < BS; ++q) {
-                mf_store_slot(&slots[(int64_t)spc * BS + q], acc[q]);
-                if constexpr (MODE == MF_DOT) dot += cur.pv[q] * acc[q];
-            }
-        }
-        if (!has1) break;
-        k += nb;
-        cur = n1;
-        n1 = n2;
-        has1 = has2;
-    }
-    return dot;
-}
-
-// the walker of the build's geometry, with its LDS
-template <int BS, int MODE>
-struct MfKernelLds {
-#if FEM_MF_WAVE
-    MfLdsW<BS, mf_fc<MODE>()> w[MF_BLOCK / 64];
-#else
-    MfLds<BS, mf_fc<MODE>()> b;
-#endif
-};
-template <int BS, int MODE>
-__device__ __forceinline__ double mf_walk_any(const MfOp& op, const double* __restrict__ x, double* __restrict__ slots,
-                                              MfKernelLds<BS, MODE>& L) {
-#if FEM_MF_WAVE
-    return mf_walk_w<BS, MODE>(op, x, slots, L.w[threadIdx.x >> 6]);
-#else
-    return mf_walk<BS, MODE>(op, x, slots, L.b);
-#endif
 }
 
 // resident workgroups of a chunk kernel (one pass of the grid over the chunks), cached per kernel

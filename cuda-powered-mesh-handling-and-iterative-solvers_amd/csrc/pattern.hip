@@ -64,10 +64,8 @@ static int inb_shift(int64_t N) {   // bucket = 128 nodes, 256 when N / 128 woul
 
 // one LDS add per distinct key for the first AGG key groups of the wave (the group of the lowest remaining lane,
 // found by one ballot), ones for the lanes left after them; returns the lane's slot for the scatter variant (base of
-// its group + rank among the lanes of the same key)
-#ifndef FEM_INC_AGG
-#define FEM_INC_AGG 1   // level 1 at 10M: 1 group 146 + 215 us, 4 groups 156 + 225, 8 groups 151 + 224
-#endif
+// its group + rank among the lanes of the same key). One group everywhere: more were no faster (level 1 at 10M:
+// 1 group 146 + 215 us, 4 groups 156 + 225, 8 groups 151 + 224).
 template <bool SCATTER, int AGG = 1>
 __device__ __forceinline__ int agg_add(int* lds, int key, bool valid) {
     const int lane = threadIdx.x & 63;
@@ -125,7 +123,7 @@ __global__ void __launch_bounds__(INB_T1) k_inc_l1(const int64_t* __restrict__ c
                 valid = false;
             }
             const int key = valid ? (int)(v >> bsh) : 0;
-            const int pos = agg_add<SCATTER, FEM_INC_AGG>(hist, key, valid);   // a wave's slots: a few buckets
+            const int pos = agg_add<SCATTER>(hist, key, valid);   // a wave's slots: a few buckets
             if (SCATTER && valid) {
                 kpair[pos] = make_int2((int32_t)v, (int32_t)i);   // (node, slot): one 8-byte store
             }
@@ -138,9 +136,6 @@ __global__ void __launch_bounds__(INB_T1) k_inc_l1(const int64_t* __restrict__ c
     }
 }
 
-#ifndef FEM_INC_NOSORT
-#define FEM_INC_NOSORT 0
-#endif
 // level 2: one workgroup per bucket; boff = the level-1 scan (bucket q's entries [boff[q G], boff[(q + 1) G]))
 __global__ void __launch_bounds__(256) k_inc_l2(const int2* __restrict__ kpair,
                                                 const int32_t* __restrict__ boff, int G, int64_t N, int bsh,
@@ -250,10 +245,6 @@ __global__ void __launch_bounds__(256) k_inc_l2(const int2* __restrict__ kpair,
             const int j = on[p];
             a = st[j];
             z = st[j + 1];
-#if FEM_INC_NOSORT   // timing builds only (wrong order): the segments left in arrival order
-            (void)j; (void)z;
-            inc[lo + p] = v;
-#else
             // rank = segment start + the number of smaller slots in the segment; four LDS reads in flight per step
             // (one dependent read per step made the ~24-long segments a chain of LDS latencies)
             int r = a, u = a;
@@ -263,7 +254,6 @@ __global__ void __launch_bounds__(256) k_inc_l2(const int2* __restrict__ kpair,
             }
             for (; u < z; ++u) r += (out[u] < v);
             inc[lo + r] = v;
-#endif
         } else {
             v = scratch[lo + p];
             int l = 0, h = B;   // segment of position p: last j with st[j] <= p
@@ -303,9 +293,7 @@ constexpr int G_HT = 512;
 __device__ __forceinline__ int32_t* ndefer_out(uint8_t* defer, int64_t N) {
     return reinterpret_cast<int32_t*>(defer) + (N + 3) / 4;
 }
-#ifndef FEM_GRAPH_LPN
-#define FEM_GRAPH_LPN 32   // k_graph_small lanes per node (two rows per wave)
-#endif
+constexpr int G_SMALL_LPN = 32;   // k_graph_small lanes per node (two rows per wave)
 
 // hash table of a row: the smallest power of two >= 2 C slots (at least 128, at most 1 << maxbits), so clearing
 // and compacting it costs ~C, not the table capacity (P1 rows: 96 candidates -> 256 slots instead of 512)
@@ -474,10 +462,7 @@ __global__ void k_graph_copy(const int32_t* __restrict__ tmp, const uint8_t* __r
 // G_UCAP + 64 keys, so probing always ends) and is marked row_len = -1 for k_graph_big; the fill pass recognises
 // those rows by their length. Rows finished by k_graph_small (defer[node] == 0) are skipped.
 constexpr int G_HT2 = 2048;
-#ifndef FEM_GRAPH_KB
-#define FEM_GRAPH_KB 4   // candidate passes whose loads k_graph issues together (1: one dependent pair per pass, A/B)
-#endif
-constexpr int G_KB = FEM_GRAPH_KB;
+constexpr int G_KB = 4;   // candidate passes whose loads k_graph issues together
 
 template <bool FILL>
 __global__ void __launch_bounds__(256) k_graph(const int64_t* __restrict__ conn, int npe,
@@ -906,33 +891,13 @@ __global__ void __launch_bounds__(256) k_sell_fill_graph(const int32_t* __restri
             sl_pattern_slice(s, lane, nslices, nrows, slice_ptr, delta, pout, ucol, uoff, G, win, cand_all[wid],
                              span);
         }
-#ifndef FEM_FILL_ROWWISE
-#define FEM_FILL_ROWWISE 1   // 10M Poisson fill pass 242 -> 188 us (0: the binary search per entry, A/B)
-#endif
-        if (FEM_FILL_ROWWISE) {
-            // CSR colidx (and csr2sell) row-wise: the lane of a row stores its own contiguous run (the wave's runs
-            // tile one contiguous block) -- no binary search of the row per entry
-            if (r < nrows) {
-                if (!dfr)
-                    for (int k = 0; k < len; ++k) colidx[rp + k] = rows[lane * TS + k];
-                if (csr2sell)
-                    for (int k = 0; k < len; ++k) csr2sell[rp + k] = e0 + (int64_t)k * 64 + lane;
-            }
-            __builtin_amdgcn_wave_barrier();
-            continue;
-        }
-        const int p0 = rp_s[wid][0], p1 = rp_s[wid][64];
-        for (int p = p0 + lane; p < p1; p += 64) {
-            int lo = 0, hi = 64;   // last row l with rp_s[l] <= p
-            while (hi - lo > 1) {
-                const int mid = (lo + hi) >> 1;
-                if (rp_s[wid][mid] <= p) lo = mid;
-                else hi = mid;
-            }
-            const int k = p - rp_s[wid][lo];
-            if (csr2sell) csr2sell[p] = e0 + (int64_t)k * 64 + lo;
-            const int64_t row = s * 64 + lo;
-            if (!defer[row]) colidx[p] = rows[lo * TS + k];
+        // CSR colidx (and csr2sell) row-wise: the lane of a row stores its own contiguous run (the wave's runs
+        // tile one contiguous block) -- no binary search of the row per entry (10M Poisson fill pass 242 -> 188 us)
+        if (r < nrows) {
+            if (!dfr)
+                for (int k = 0; k < len; ++k) colidx[rp + k] = rows[lane * TS + k];
+            if (csr2sell)
+                for (int k = 0; k < len; ++k) csr2sell[rp + k] = e0 + (int64_t)k * 64 + lane;
         }
         __builtin_amdgcn_wave_barrier();   // the staged rows consumed before the next slice overwrites them
     }
@@ -1175,7 +1140,7 @@ int fem_graph_count2(const int64_t* conn, int npe, const int32_t* inc_ptr, const
     FEM_HIP(hipMemsetAsync(tmp + N * G_TCAP + (N + 3) / 4, 0, sizeof(int32_t), S(stream)));   // deferred rows
     const bool al16 = (reinterpret_cast<uintptr_t>(conn) & 15) == 0;
 #define GS_LAUNCH(NPE_)                                                                                           \
-    hipLaunchKernelGGL((k_graph_small<FEM_GRAPH_LPN, NPE_>), dim3((unsigned)grid), dim3(256), 0, S(stream), conn, \
+    hipLaunchKernelGGL((k_graph_small<G_SMALL_LPN, NPE_>), dim3((unsigned)grid), dim3(256), 0, S(stream), conn, \
                        npe, inc_ptr, inc, N, row_len, tmp, defer_flags(tmp, N), overflow)
     if (al16 && npe == 4 && getenv("FEM355_GRAPH_SLOTS") == nullptr) GS_LAUNCH(4);
     else if (al16 && npe == 6) GS_LAUNCH(6);

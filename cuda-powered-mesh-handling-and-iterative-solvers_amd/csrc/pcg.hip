@@ -54,15 +54,9 @@ struct VecFusedP {
 // along lines the x gathers of neighbouring lanes are contiguous too. U entries per step: all U column loads,
 // then U value loads, then U gathers are in flight together; the tail step is predicated.
 // CI = int32_t: absolute block columns; CI = int16_t: 16-bit deltas col - row (half the index bytes)
-#ifndef FEM_SPMV_UB
-#define FEM_SPMV_UB 1
-#endif
-constexpr int SPMV_UB = FEM_SPMV_UB;   // bs > 1: blocks in flight per lane
-#ifndef FEM_SPMV_NT3
-#define FEM_SPMV_NT3 1
-#endif
-constexpr bool SPMV_NT3 = FEM_SPMV_NT3;   // bs > 1 in the PCG kernels: nontemporal matrix loads keep the p
-                                          // gather window in L2 (10M elastic K1 420 -> 406 us, PMC 1.115x alg)
+constexpr int SPMV_UB = 1;        // bs > 1: blocks in flight per lane
+constexpr bool SPMV_NT3 = true;   // bs > 1 in the PCG kernels: nontemporal matrix loads keep the p
+                                  // gather window in L2 (10M elastic K1 420 -> 406 us, PMC 1.115x alg)
 
 template <int BS, int U, bool NT, typename X, typename CI = int32_t>
 __device__ __forceinline__ void sell_row(int64_t s, int lane, const int64_t* __restrict__ slice_ptr,
@@ -144,18 +138,13 @@ constexpr int SPMV_UP = 8;  // pairs in flight of the paired layout (tools/spmv_
 // SpMV row of the 16-byte-value copy of the matrix: bs = 1 lane-paired layout (sell_pair.hpp), bs = 3 plane-paired
 // layout A (sell_pair3.hpp: 4 sixteen-byte + 1 eight-byte value loads per block, nontemporal; tools/spmv3_layout.py:
 // 10M elastic 369 -> 348 us stand-alone). Both keep the plain layout's per-row summation order.
-#ifndef FEM_K1_U3
-#define FEM_K1_U3 1   // bs = 3 blocks in flight per lane (layout A)
-#endif
-#ifndef FEM_K1_G3
-#define FEM_K1_G3 0   // bs = 3 gathers: 0 = three 8-byte loads, 1 = 8 + 16 bytes
-#endif
+// bs = 3: one block in flight per lane, the gathers as three 8-byte loads (sell3_row_a's default).
 template <int BS>
 __device__ __forceinline__ void sell_row_paired(int64_t s, int lane, const int64_t* __restrict__ slice_ptr,
                                                 const int16_t* __restrict__ cols, const double* __restrict__ vals,
                                                 const double* __restrict__ x, double out[BS]) {
     if constexpr (BS == 1) out[0] = sell_row_pair<SPMV_UP>(s, lane, slice_ptr, cols, vals, x);
-    else sell3_row_a<FEM_K1_U3, SPMV_NT3, FEM_K1_G3>(s, lane, slice_ptr, cols, vals, x, out);
+    else sell3_row_a<1, SPMV_NT3>(s, lane, slice_ptr, cols, vals, x, out);
 }
 
 template <int BS, int U = SPMV_U, bool NT = false, typename CI = int32_t>
@@ -514,13 +503,11 @@ __device__ __forceinline__ bool u2_release(double acc, PcgState* __restrict__ st
             __hip_atomic_store(reinterpret_cast<double*>(sync + U2_BC) + 1, halt, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
             // the broadcast's write-through stores drained before the release (the guide's sc1 hand-off form; the
-            // asm's memory clobber also keeps the compiler from moving them past the swap); FEM_MM_ACQREL: a release
-            // swap instead
+            // asm's memory clobber also keeps the compiler from moving them past the swap)
             fem_drain_stores();
             unsigned expect = e - 1;
-            if (!__hip_atomic_compare_exchange_strong(sync + U2_REL, &expect, e,
-                                                      FEM_MM_ACQREL ? __ATOMIC_RELEASE : __ATOMIC_RELAXED,
-                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+            if (!__hip_atomic_compare_exchange_strong(sync + U2_REL, &expect, e, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT)) {
                 // a waiter gave up first: undo the commit (the iteration did not complete) and keep its verdict
                 st->iter = it0;
                 u2_give_up(st, e);
@@ -544,13 +531,8 @@ __device__ __forceinline__ bool u2_release(double acc, PcgState* __restrict__ st
                 __builtin_amdgcn_s_sleep(2);
             }
             // no load below may be moved above the poll by the compiler (the hardware issues it only after the
-            // branch on the polled value); the broadcast is read with write-through (sc1) loads. FEM_MM_ACQREL: one
-            // agent-scope acquire after the poll matched
-#if FEM_MM_ACQREL
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#else
+            // branch on the polled value); the broadcast is read with write-through (sc1) loads
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#endif
             if (v == e) {
                 beta_ = __hip_atomic_load(reinterpret_cast<const double*>(sync + U2_BC), __ATOMIC_RELAXED,
                                          __HIP_MEMORY_SCOPE_AGENT);
@@ -684,34 +666,25 @@ __global__ void __launch_bounds__(PCG_BLOCK) k_pcg_update2(int64_t n, double* __
 // the array k_mf_gather wrote (the A/B form; the same bits again). The release protocol is k_pcg_update2's, and so is
 // the order of every other operation: given equal q the update is bit-identical to k_pcg_update2's.
 // (Round 5 ran one node per thread-step: three 8-byte accesses per vector 24 bytes apart across the lanes, 93 us for
-// the 10M elastic cube's 380 MB.)
-#ifndef FEM_MF_NTL
-#define FEM_MF_NTL 0   // 1: the merged update reads the slots with non-temporal loads (read once)
-#endif
+// the 10M elastic cube's 380 MB.) Non-temporal slot loads measured slower: the update reads the slots partly from L2 /
+// MALL (profiles/r04f_mf_nontemporal_ab.log).
 // The first MF_QK slots of the node are loaded unconditionally (indices clamped to the node's last slot) and the ones
 // past its count added as +0.0 -- the same bits (a sum started from +0.0 is never -0.0, and x + 0.0 == x otherwise),
 // but the loads of all the thread's register-cached steps go out together instead of one dependent loop per dof
 // (nodes have 2.06 slots on average on the 10M cube; more than MF_QK continue in a loop)
 constexpr int MF_QK = 4;
-#ifndef FEM_MF_QK_ON
-#define FEM_MF_QK_ON 1   // 0: the plain loop (A/B)
-#endif
 template <int BS>
 __device__ __forceinline__ double mf_q_dof(const MfOp& op, const double* __restrict__ slots, int64_t d) {
     const int64_t a = d / BS;
     const int c = (int)(d - a * BS);
     const int k0 = op.nptr[a], k1 = op.nptr[a + 1];
     double s = 0.0;
-    if (FEM_MF_QK_ON && op.spos && k1 > k0) {   // node-major slots: the node's slots are k0 .. k1 - 1
+    if (op.spos && k1 > k0) {   // node-major slots: the node's slots are k0 .. k1 - 1
         double v[MF_QK];
 #pragma unroll
         for (int q = 0; q < MF_QK; ++q) {
             const int k = k0 + q < k1 ? k0 + q : k1 - 1;
-#if FEM_MF_NTL
-            v[q] = __builtin_nontemporal_load(&slots[(int64_t)k * BS + c]);
-#else
             v[q] = slots[(int64_t)k * BS + c];
-#endif
         }
 #pragma unroll
         for (int q = 0; q < MF_QK; ++q) s += k0 + q < k1 ? v[q] : 0.0;
@@ -720,66 +693,14 @@ __device__ __forceinline__ double mf_q_dof(const MfOp& op, const double* __restr
     }
     for (int k = k0; k < k1; ++k) {
         const int64_t sl = op.spos ? k : op.nslot[k];
-#if FEM_MF_NTL
-        s += __builtin_nontemporal_load(&slots[sl * BS + c]);
-#else
         s += slots[sl * BS + c];
-#endif
     }
     return s;
 }
 
-// FEM_MF_QLDS = 1 (A/B): the slot values a wave's 128 dofs of one thread-step need -- one contiguous node-major range --
-// staged into LDS by 16-byte lanes first (2-3 coalesced wave loads instead of 8 scattered 8-byte ones per dof pair),
-// then summed from LDS in the same order (the same bits); ranges over MF_QCAP doubles take the direct loads.
-// Measured slightly slower than the fixed-count direct loads (update 75.8-78.1 vs 73.4-75.9 us on the 10M elastic
-// cube, profiles/r06l_mf_qlds_prof_ab.txt: the staging serialises a wave's thread-steps); off
-#ifndef FEM_MF_QLDS
-#define FEM_MF_QLDS 0
-#endif
-constexpr int MF_QCAP = 512;
-template <int BS>
-__device__ __forceinline__ bool mf_q_stage(const MfOp& op, const double* __restrict__ slots, double* qs, int64_t iw,
-                                           int64_t i, int64_t n, int lane, double2& qv) {
-    const int64_t d_lo = 2 * iw, d_hi = (2 * iw + 128 < n ? 2 * iw + 128 : n) - 1;
-    const int64_t a_lo = d_lo / BS, a_hi = d_hi / BS;
-    const int s_lo = op.nptr[a_lo], s_hi = op.nptr[a_hi + 1];
-    const int64_t st0 = ((int64_t)BS * s_lo) & ~(int64_t)1;
-    const int len = (int)((int64_t)BS * s_hi - st0);
-    if (len > MF_QCAP) return false;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the previous step's LDS reads of this wave are done
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    const double2* s2 = reinterpret_cast<const double2*>(slots + st0);
-    for (int t = lane; 2 * t < len; t += 64) {
-        if (2 * t + 1 < len) {
-            const double2 v = s2[t];
-            qs[2 * t] = v.x;
-            qs[2 * t + 1] = v.y;
-        } else {
-            qs[2 * t] = slots[st0 + 2 * t];
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    double q[2] = {0.0, 0.0};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int64_t d = 2 * i + h;
-        if (d < n) {
-            const int64_t a = d / BS;
-            const int c = (int)(d - a * BS);
-            const int k0 = op.nptr[a], k1 = op.nptr[a + 1];
-            double sum = 0.0;
-            for (int k = k0; k < k1; ++k) sum += qs[(int64_t)BS * k + c - st0];
-            q[h] = sum;
-        }
-    }
-    qv = make_double2(q[0], q[1]);
-    return true;
-}
-
+// (Staging a wave's contiguous node-major slot range into LDS first and summing from there measured slightly slower
+// than these fixed-count direct loads: update 75.8-78.1 vs 73.4-75.9 us on the 10M elastic cube,
+// profiles/r06l_mf_qlds_prof_ab.txt.)
 template <int BS, bool FROM_Q>
 __global__ void __launch_bounds__(PCG_BLOCK) k_pcg_update2_mf(int64_t nn, double* __restrict__ x, double* __restrict__ p,
                                                               double* __restrict__ r, const double* __restrict__ q,
@@ -807,19 +728,10 @@ __global__ void __launch_bounds__(PCG_BLOCK) k_pcg_update2_mf(int64_t nn, double
     const double2* q2 = reinterpret_cast<const double2*>(q);
     const double2* w2 = reinterpret_cast<const double2*>(w);
     double2* r2 = reinterpret_cast<double2*>(r);
-    constexpr bool QL = FEM_MF_QLDS && !FROM_Q;
-    __shared__ double qst[QL ? PCG_BLOCK / 64 : 1][QL ? MF_QCAP : 1];
     const int lane = threadIdx.x & 63;
-    double* qs = qst[QL ? (threadIdx.x >> 6) : 0];
-    // q of the pair (2 i, 2 i + 1): staged when the node-major slots allow (every lane of the wave calls it: the wave's
-    // first pair iw is uniform), else the direct fixed-count loads
+    // q of the pair (2 i, 2 i + 1)
     auto qpair = [&](int64_t i) -> double2 {
         if constexpr (FROM_Q) return q2[i];
-        if constexpr (QL) {
-            double2 qv;
-            const int64_t iw = i - lane;
-            if (op.spos && iw < n2 && mf_q_stage<BS>(op, slots, qs, iw, i, n, lane, qv)) return qv;
-        }
         if (i >= n2) return make_double2(0.0, 0.0);
         return make_double2(mf_q_dof<BS>(op, slots, 2 * i), mf_q_dof<BS>(op, slots, 2 * i + 1));
     };
@@ -829,7 +741,7 @@ __global__ void __launch_bounds__(PCG_BLOCK) k_pcg_update2_mf(int64_t nn, double
     for (int k = 0; k < U2_NPT; ++k) {
         const int64_t i = i0 + k * stride;
         z[k] = make_double2(0.0, 0.0);
-        const double2 qv = qpair(i);   // the whole wave (staging)
+        const double2 qv = qpair(i);
         if (i < n2) {
             double2 rv = r2[i], wv = w2[i];
             rv.x = rv.x - alpha * qv.x;
@@ -844,8 +756,8 @@ __global__ void __launch_bounds__(PCG_BLOCK) k_pcg_update2_mf(int64_t nn, double
             acc += rv.y * z[k].y;
         }
     }
-    for (int64_t ib = i0 - lane + U2_NPT * stride; ib < n2; ib += stride) {   // past the register capacity (the
-        const int64_t i = ib + lane;                                           // wave together: staging)
+    for (int64_t ib = i0 - lane + U2_NPT * stride; ib < n2; ib += stride) {   // past the register capacity
+        const int64_t i = ib + lane;
         const double2 qv = qpair(i);
         if (i >= n2) continue;
         double2 rv = r2[i], wv = w2[i];
@@ -1343,11 +1255,8 @@ __device__ __forceinline__ void cg1_commit(PcgState* st, const Cg1Step& k, doubl
 // reduction and one more launch, so it wins on large partitions only (world-1 RCCL lines, round 6: 1.73M nodes 285.5
 // vs 302.7 us per iteration, 216k nodes -- the N = 8 rank share of the 10M cube -- 55.2 vs 53.8 us): chosen per
 // context at fem_pcg_set_operator_mf when the partition has at least MF_NOGATHER_MIN_NODES nodes (the linear fit of
-// the two points crosses at ~330k). FEM_MF_DIST_NOGATHER = 0 / 1 (build) or FEM355_MF_NOGATHER=0 / 1 (run) force
+// the two points crosses at ~330k). FEM355_MF_NOGATHER=0 / 1 (run) forces
 // either form. Both pack the same exchange message, so ranks may differ in the form they run.
-#ifndef FEM_MF_DIST_NOGATHER
-#define FEM_MF_DIST_NOGATHER -1
-#endif
 constexpr int64_t MF_NOGATHER_MIN_NODES = 400000;
 // Every vector read and written as 16-byte lanes (a double2 of dofs per thread-step; round 5: one 8-byte dof per
 // thread), the per-dof arithmetic unchanged. MF: v from the element-chunk operator's slots (never stored)
@@ -2040,7 +1949,7 @@ struct fem_pcg {
     fem_mf* mf;
     double* mf_sl;  // this context's slot buffer [nslots * bs] (no other context or stream writes it)
     int64_t mf_sl_cap;   // doubles mf_sl holds (a later operator with more slots reallocates it)
-    int mf_nogather;     // distributed element-chunk iteration: the gather-free form (FEM_MF_DIST_NOGATHER)
+    int mf_nogather;     // distributed element-chunk iteration: the gather-free form (MF_NOGATHER_MIN_NODES)
     int mf_qfuse;   // the merged update reads q from the slots (no gather launch); set per launch of K1 + update2
 };
 
@@ -2067,12 +1976,12 @@ template <int BS>
 __global__ void __launch_bounds__(MF_BLOCK) k_pcg_mf_dot(MfOp op, const double* __restrict__ p,
                                                          double* __restrict__ slots, PcgState* __restrict__ st,
                                                          RedBuf red) {
-    __shared__ MfKernelLds<BS, MF_DOT> L;
+    __shared__ MfLds<BS> L;
     __shared__ double lds4[MF_BLOCK / 64];
     __shared__ int flag;
     if (blockIdx.x == 0 && threadIdx.x == 0) st->xupd = 0;
     if (st->halt || st->iter >= st->max_iter) return;
-    double dot = mf_walk_any<BS, MF_DOT>(op, p, slots, L);
+    double dot = mf_walk<BS, MF_DOT>(op, p, slots, L);
     dot = block_sum<MF_BLOCK>(dot, lds4);
     double pq;
     if (reduce_grid<MF_BLOCK>(dot, red.part(RED_K1), red.cnt(RED_K1), &pq, lds4, &flag) && threadIdx.x == 0)
@@ -2090,36 +1999,36 @@ __global__ void __launch_bounds__(MF_BLOCK) k_cg1_mf_slots(MfOp op, const double
                                                            double* __restrict__ slots, const PcgState* __restrict__ st,
                                                            int always, P2PArgs xp, const double* __restrict__ recv,
                                                            const double* __restrict__ send, int64_t off) {
-    __shared__ MfKernelLds<BS, MF_APPLY> L;
+    __shared__ MfLds<BS> L;
     if (!always) {   // the step of this pass, from the unchanged state (committed by k_cg1_mf_gather)
         const Cg1Step k = cg1_eval(st, cg1_scalar(recv, send, off, 0, xp), cg1_scalar(recv, send, off, 1, xp));
         if (!k.go) return;
     }
-    (void)mf_walk_any<BS, MF_APPLY>(op, u, slots, L);
+    (void)mf_walk<BS, MF_APPLY>(op, u, slots, L);
 }
 
-// FEM_MF_DIST_NOGATHER: the walk also reduces d = u.v (sum over the slots of u_node . slot) -> st->red[0]
+// mf_nogather: the walk also reduces d = u.v (sum over the slots of u_node . slot) -> st->red[0]
 template <int BS>
 __global__ void __launch_bounds__(MF_BLOCK) k_cg1_mf_slots_dot(MfOp op, const double* __restrict__ u,
                                                                double* __restrict__ slots, PcgState* __restrict__ st,
                                                                int always, P2PArgs xp, const double* __restrict__ recv,
                                                                const double* __restrict__ send, int64_t off,
                                                                RedBuf red) {
-    __shared__ MfKernelLds<BS, MF_DOT> L;
+    __shared__ MfLds<BS> L;
     __shared__ double lds4[MF_BLOCK / 64];
     __shared__ int flag;
     if (!always) {   // the step of this pass, from the unchanged state (committed by k_cg1_mf_iface)
         const Cg1Step k = cg1_eval(st, cg1_scalar(recv, send, off, 0, xp), cg1_scalar(recv, send, off, 1, xp));
         if (!k.go) return;
     }
-    double dot = mf_walk_any<BS, MF_DOT>(op, u, slots, L);
+    double dot = mf_walk<BS, MF_DOT>(op, u, slots, L);
     dot = block_sum<MF_BLOCK>(dot, lds4);
     double d;
     if (reduce_grid<MF_BLOCK>(dot, red.part(RED_K1), red.cnt(RED_K1), &d, lds4, &flag) && threadIdx.x == 0)
         st->red[0] = d;
 }
 
-// FEM_MF_DIST_NOGATHER: the interface rows only -- their slot sums packed for the exchange -- and [g, d]; the last
+// mf_nogather: the interface rows only -- their slot sums packed for the exchange -- and [g, d]; the last
 // block commits the step
 template <int BS>
 __global__ void __launch_bounds__(PCG_BLOCK) k_cg1_mf_iface(MfOp op, const double* __restrict__ slots,
@@ -2194,7 +2103,7 @@ __global__ void __launch_bounds__(PCG_BLOCK) k_cg1_mf_gather(MfOp op, const doub
 #pragma unroll
         for (int c = 0; c < BS; ++c) o[c] = 0.0;
         const int k0 = op.nptr[a], k1 = op.nptr[a + 1];
-        if (FEM_MF_QK_ON && op.spos && k1 > k0) {   // the update's fixed-count loads (mf_q_dof): the same bits
+        if (op.spos && k1 > k0) {   // the update's fixed-count loads (mf_q_dof): the same bits
             double v[MF_QK][BS];
 #pragma unroll
             for (int q = 0; q < MF_QK; ++q) {
@@ -2466,9 +2375,6 @@ static const void* c1f_fn(const fem_pcg* s) {
 // repeated solves on one matrix ask for the same sizes. At most PCG_CACHE_KEEP bytes are kept (oldest freed first).
 // RCCL buffers and bs = 3 contexts keep plain hipMalloc: with recycled buffers the 10M elastic SpMV ran 311 -> 367 us
 // (whatever the match order; cause not found), for 1 ms less teardown.
-#ifndef FEM_PCG_POOL
-#define FEM_PCG_POOL 1
-#endif
 // cap of the cache (FEM355_PCG_CACHE_MB, default 1024 MB: a 10M-row bs = 1 context with its paired matrix copy is
 // ~330 MB); fem_pcg_release_cache() hands everything back to the driver (the Python layer calls it at exit and
 // before retrying a failed allocation)
@@ -2494,7 +2400,7 @@ size_t dev_cache_bytes = 0;
 }  // namespace
 
 static hipError_t pool_alloc(void** p, size_t bytes, hipStream_t, bool cached) {
-    if (!FEM_PCG_POOL || !cached) return hipMalloc(p, bytes);
+    if (!cached) return hipMalloc(p, bytes);
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -2517,10 +2423,6 @@ static hipError_t pool_alloc(void** p, size_t bytes, hipStream_t, bool cached) {
 // the caller's stream must not use p any more: the buffer can be handed to another context at once
 static void pool_free(void* p, hipStream_t st) {
     if (!p) return;
-    if (!FEM_PCG_POOL) {
-        (void)hipFree(p);
-        return;
-    }
     (void)hipStreamSynchronize(st);
     std::lock_guard<std::mutex> g(dev_cache_mu);
     for (size_t i = 0; i < dev_live.size(); ++i) {
@@ -3251,9 +3153,7 @@ int fem_pcg_set_operator_mf(fem_pcg* s, fem_mf* m) {
     s->mf = m;
     {
         const char* e = getenv("FEM355_MF_NOGATHER");
-        s->mf_nogather = e ? (atoi(e) != 0)
-                           : FEM_MF_DIST_NOGATHER >= 0 ? FEM_MF_DIST_NOGATHER
-                                                       : (int)(mf_nodes(m) >= MF_NOGATHER_MIN_NODES);
+        s->mf_nogather = e ? (atoi(e) != 0) : (int)(mf_nodes(m) >= MF_NOGATHER_MIN_NODES);
     }
     s->fused = s->deferred = s->persist_req = s->persist_fit_only = s->persist = 0;
     s->cols16 = nullptr;

@@ -29,10 +29,6 @@
 
 namespace fem {
 
-#ifndef FEM_GV_PROBE
-#define FEM_GV_PROBE 0   // timing builds only (wrong results): 1 no barrier wait in the loop, 2 no m-flag wait
-#endif
-
 struct GvArgs {
     double* u;     // M^-1 r by recurrence
     double* w;     // A u by recurrence
@@ -44,24 +40,13 @@ struct GvArgs {
     int64_t moff[2];   // DIST: byte offsets of m[0] / m[1] in every rank's comm block (m[i] = own block + moff[i])
 };
 
-#ifndef FEM_GV_U1
-#define FEM_GV_U1 8   // one-slot build: lane pairs in flight per slice
-#endif
-#ifndef FEM_GV_SYNCWAVE
-#define FEM_GV_SYNCWAVE 0   // measured neutral (profiles/r06za_gv_syncwave_ab.txt): off
-#endif
-#ifndef FEM_GV_EARLY
-#define FEM_GV_EARLY 1   // post gamma / delta and arrive before the x update and the m hand-off
-#endif
-constexpr bool GV_EARLY = FEM_GV_EARLY;
+constexpr int GV_U1 = 8;     // one-slot build: lane pairs in flight per slice
 constexpr int GV_MAXS = 2;   // slices per wave (packed assignment)
 // LDS: head (wave sums of gamma [0, 16), the ok word, the barrier sums [18, 20), wave sums of delta [20, 36)), then x
 // and the Jacobi weights of the workgroup's rows
 constexpr size_t GV_LDS_HEAD = 512;
-#ifndef FEM_GV_BIGLDS
-#define FEM_GV_BIGLDS 0   // A/B: the single-reduction LDS size; measured no different (profiles/r06zb_gv_biglds_ab.txt)
-#endif
-constexpr size_t GV_LDS = FEM_GV_BIGLDS ? PK_LDS : GV_LDS_HEAD + sizeof(double) * 2 * GV_MAXS * PK_WAVES * 64;
+// (the single-reduction kernel's larger PK_LDS measured no different: profiles/r06zb_gv_biglds_ab.txt)
+constexpr size_t GV_LDS = GV_LDS_HEAD + sizeof(double) * 2 * GV_MAXS * PK_WAVES * 64;
 
 // arrival of this workgroup on the grid barrier of epoch e (thread 0; the caller drained the partial stores):
 // pk_barrier's counters -- the arrival that completes a group adds to the 8 replicas of the top counter
@@ -69,11 +54,7 @@ __device__ __forceinline__ void gv_arrive(unsigned* sy, int grp, unsigned nper, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned old = __hip_atomic_fetch_add(sy + PK_GRP + grp * PK_LINE, 1u, __ATOMIC_RELAXED,
                                                 __HIP_MEMORY_SCOPE_AGENT);
-#if FEM_GV_PROBE   // (timing builds: workgroups run epochs apart, so whichever add completes a group's count bumps)
-    if ((old + 1) % nper == 0)
-#else
     if (old == e * nper - 1)
-#endif
         for (int r = 0; r < NXCD; ++r)
             __hip_atomic_fetch_add(sy + PK_GEN + r * PK_LINE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -234,7 +215,7 @@ template <int MAXS, bool DIST = false>
 __global__ void __launch_bounds__(PK_T) k_pcg_persist_gv(PkArgs a, GvArgs gv) {
     static_assert(MAXS >= 1 && MAXS <= GV_MAXS, "slots per wave");
     // lane pairs in flight per slice (pk_u: 8 for one slot, 4 for two)
-    constexpr int GU = MAXS == 1 ? FEM_GV_U1 : pk_u<MAXS, false>();
+    constexpr int GU = MAXS == 1 ? GV_U1 : pk_u<MAXS, false>();
     static_assert(GV_LDS_HEAD >= sizeof(double) * (2 * PK_WAVES + 4), "LDS head: two sets of wave sums");
     extern __shared__ __attribute__((aligned(16))) double pk_lds_raw[];
     double* lds16 = pk_lds_raw;
@@ -250,10 +231,9 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist_gv(PkArgs a, GvArgs gv) {
     // packed assignment: a.pack (<= MAXS, host) slices per wave in order
     const int sL0 = (int)((int64_t)L * a.nslices / G);
     const int nL = (int)((int64_t)(L + 1) * a.nslices / G) - sL0;
-    // FEM_GV_SYNCWAVE: when the workgroup's slices leave a wave free, wave 0 takes none -- it is the wave that polls
-    // the grid barrier, which it then does while the other waves run the SpMV (the sums are read under it too)
-    const int wsl = (FEM_GV_SYNCWAVE && nL <= (PK_WAVES - 1) * a.pack) ? wv - 1 : wv;
-    const int lo = wsl < 0 ? nL : (wsl * a.pack < nL ? wsl * a.pack : nL);
+    // (keeping wave 0, the wave that polls the grid barrier, free of slices where the workgroup's slices allow
+    // measured neutral: profiles/r06za_gv_syncwave_ab.txt)
+    const int lo = wv * a.pack < nL ? wv * a.pack : nL;
     const int s0 = sL0 + lo + (DIST ? (int)a.sbase : 0);   // DIST: this rank's slices start at global slice sbase
     const int nreg = nL - lo < a.pack ? nL - lo : a.pack;
     const int nrows = (int)a.nrows;
@@ -316,7 +296,6 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist_gv(PkArgs a, GvArgs gv) {
     const double* vap = pk_launder(a.vals);
     const int32_t* uop = a.uoff ? pk_launder(a.uoff) : nullptr;
     const int16_t* ucp = a.uoff ? pk_launder(a.ucol) : nullptr;
-    static_assert(!DIST || GV_EARLY, "the distributed build posts its arrival in the update");
     // n[j] = (A v)[rows of slot j]: a workgroup whose gather window reaches other ranks reads their rows past this
     // GPU's L2 (mode 3, as k_pcg_persist's DIST build)
     auto spmv = [&](const double* v, double* out) {
@@ -375,7 +354,7 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist_gv(PkArgs a, GvArgs gv) {
     };
     // wave 0 waits for the flags of the gather window to reach e (bounded; a give-up fails the launch)
     auto wait_window = [&](unsigned e) -> bool {
-        if (wv == 0 && !(FEM_GV_PROBE & 2)) {   // (probe 2, timing only: no m-flag wait)
+        if (wv == 0) {
             bool ok = true;
             for (int b0 = wlo; b0 <= whi && ok; b0 += 64) {
                 const int jw = b0 + lane;
@@ -517,8 +496,7 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist_gv(PkArgs a, GvArgs gv) {
     int k = 0;
     if (!halt && !fail) {
         for (k = 0; k < a.kmax; ++k) {
-            // ---- the arrival of this iteration (its partials were posted by the last update), then the m window
-            if (!GV_EARLY && k > 0 && threadIdx.x == 0) gv_arrive(sy, grp, nper, ep);
+            // ---- the m window (the arrival of this iteration was posted by the last update)
             if (!wait_window(ep)) {
                 fail = true;
                 break;
@@ -526,7 +504,7 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist_gv(PkArgs a, GvArgs gv) {
             // ---- n = A m (m of this iteration's parity), while the barrier completes
             spmv(pk_launder((it & 1) ? gv.m[1] : gv.m[0]), nn);   // (no dynamic kernarg index)
             // ---- gamma, delta of this iterate
-            if (k > 0 && !(FEM_GV_PROBE & 1)) {   // (probe 1, timing only: no wait, stale scalars)
+            if (k > 0) {
                 if (!wait_sums(ep)) {
                     fail = true;
                     break;
@@ -568,73 +546,43 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist_gv(PkArgs a, GvArgs gv) {
             unsigned rbi = rb;
             asm volatile("" : "+v"(rbi));
             const unsigned e = ep + 1;
-            if constexpr (GV_EARLY) {
-                // the vectors gamma / delta need first, their partials posted and the arrival on barrier e made at
-                // once; x and the hand-off of m follow (the arrival no longer waits for the m stores to drain)
+            // the vectors gamma / delta need first, their partials posted and the arrival on barrier e made at
+            // once; x and the hand-off of m follow (the arrival no longer waits for the m stores to drain)
 #pragma unroll
-                for (int j = 0; j < MAXS; ++j) {
-                    if (j < nreg) {
-                        zz[j] = nn[j] + bnew * zz[j];
-                        qq[j] = mm[j] + bnew * qq[j];
-                        ss[j] = ww[j] + bnew * ss[j];
-                        pp[j] = uu[j] + bnew * pp[j];
-                        rr[j] = rr[j] - al * ss[j];
-                        uu[j] = uu[j] - al * qq[j];
-                        ww[j] = ww[j] - al * zz[j];
-                        gp += rr[j] * uu[j];
-                        dp += ww[j] * uu[j];
-                    }
-                }
-                double gs = 0.0, ds = 0.0;
-                gv_block_sums(gp, dp, lds16, &gs, &ds, false);
-                post_arrive(e, gs, ds);
-                const int64_t moff = (it & 1) ? gv.moff[0] : gv.moff[1];
-#pragma unroll
-                for (int j = 0; j < MAXS; ++j) {
-                    if (j < nreg) {
-                        xl[j * 64] += al * pp[j];
-                        mm[j] = wl[j * 64] * ww[j];
-                        if (GV_ON(j)) put_row(mst, moff, rbi + 64u * j, mm[j]);
-                    }
-                }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave drains its m stores
-                __syncthreads();
-                if (threadIdx.x == 0) raise_flag(e);
-            } else {
-#pragma unroll
-                for (int j = 0; j < MAXS; ++j) {
-                    if (j < nreg) {
-                        zz[j] = nn[j] + bnew * zz[j];
-                        qq[j] = mm[j] + bnew * qq[j];
-                        ss[j] = ww[j] + bnew * ss[j];
-                        pp[j] = uu[j] + bnew * pp[j];
-                        xl[j * 64] += al * pp[j];
-                        rr[j] = rr[j] - al * ss[j];
-                        uu[j] = uu[j] - al * qq[j];
-                        ww[j] = ww[j] - al * zz[j];
-                        mm[j] = wl[j * 64] * ww[j];
-                        if (GV_ON(j))
-                            __hip_atomic_store(mst + (rbi + 64u * j), mm[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        gp += rr[j] * uu[j];
-                        dp += ww[j] * uu[j];
-                    }
-                }
-                double gs = 0.0, ds = 0.0;
-                gv_block_sums(gp, dp, lds16, &gs, &ds, true);   // (every wave drained its m stores)
-                if (threadIdx.x == 0) {
-                    double* pb = a.part + (size_t)(e & 1u) * 2 * G;
-                    __hip_atomic_store(pb + L, gs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(pb + G + L, ds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    pk_st(uf + L * PK_LINE, e);
+            for (int j = 0; j < MAXS; ++j) {
+                if (j < nreg) {
+                    zz[j] = nn[j] + bnew * zz[j];
+                    qq[j] = mm[j] + bnew * qq[j];
+                    ss[j] = ww[j] + bnew * ss[j];
+                    pp[j] = uu[j] + bnew * pp[j];
+                    rr[j] = rr[j] - al * ss[j];
+                    uu[j] = uu[j] - al * qq[j];
+                    ww[j] = ww[j] - al * zz[j];
+                    gp += rr[j] * uu[j];
+                    dp += ww[j] * uu[j];
                 }
             }
+            double gs = 0.0, ds = 0.0;
+            gv_block_sums(gp, dp, lds16, &gs, &ds, false);
+            post_arrive(e, gs, ds);
+            const int64_t moff = (it & 1) ? gv.moff[0] : gv.moff[1];
+#pragma unroll
+            for (int j = 0; j < MAXS; ++j) {
+                if (j < nreg) {
+                    xl[j * 64] += al * pp[j];
+                    mm[j] = wl[j * 64] * ww[j];
+                    if (GV_ON(j)) put_row(mst, moff, rbi + 64u * j, mm[j]);
+                }
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave drains its m stores
+            __syncthreads();
+            if (threadIdx.x == 0) raise_flag(e);
             it += 1;
             ep = e;
         }
     }
     // ---- chunk end without a stop: reduce the posted gamma / delta (the next launch starts from them); stop test
     if (!fail && !halt && k == a.kmax && a.kmax > 0) {
-        if (!GV_EARLY && threadIdx.x == 0) gv_arrive(sy, grp, nper, ep);   // (GV_EARLY: arrived in the update)
         if (!wait_sums(ep)) {
             fail = true;
         } else {

@@ -89,14 +89,8 @@ __device__ __forceinline__ void pk_slice_span(int64_t s, int64_t nrows, int dmin
 
 // a slice's lane-paired 16-bit deltas (pair_pos) written as one 32-bit store per pair (entries 2 k2, 2 k2 + 1 of lane
 // l are adjacent halves), then the unpaired last entry of an odd width: full 256-byte rows per store instruction
-#ifndef FEM_SL_SKIP
-#define FEM_SL_SKIP 0
-#endif
 template <class Delta>
 __device__ __forceinline__ void sl_store_pairs(int16_t* __restrict__ out, int w, int l, const Delta& delta) {
-#if FEM_SL_SKIP & 2
-    return;
-#endif
     const int np = w >> 1;
     int32_t* o32 = reinterpret_cast<int32_t*>(out);   // out = pout + slice start: 128-byte aligned
     for (int k2 = 0; k2 < np; ++k2)
@@ -117,15 +111,9 @@ __device__ __forceinline__ void sl_pattern_slice(int64_t s, int l, int64_t nslic
                                                  int16_t* __restrict__ pout, int16_t* __restrict__ ucol,
                                                  int32_t* __restrict__ uoff, int G, int* __restrict__ win, int* cand,
                                                  int2* __restrict__ span = nullptr) {
-#if FEM_SL_SKIP & 4   // timing builds only (wrong layout): the fill pass without the solver layout
-    return;
-#endif
     const int64_t p0 = slice_ptr[s];
     const int w = (int)((slice_ptr[s + 1] - p0) >> 6);
     const int64_t row = s * 64 + l;
-#if FEM_SL_SKIP & 1
-    G = 0;
-#endif
     if (G > 0) {   // gather window (k_pk_window): the delta union of the slice over its owner workgroup
         int dmin = 0, dmax = 0;
         if (row < nrows)

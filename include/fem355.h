@@ -725,11 +725,6 @@ int fem_mf_destroy(fem_mf* m);
 int fem_mf_apply(fem_mf* m, const double* x, double* y, fem_stream_t stream);
 /* d = diag(K) [N*bs] (the exact diagonal) */
 int fem_mf_diag(fem_mf* m, double* d, fem_stream_t stream);
-/* debug builds only (-DFEM_MF_SPCHECK=1, tools/mf_spcheck.py): the stand-alone applications also carry each slot
- * position through the chunk walk's prefetch records and compare it at every store with the one read under the chunk;
- * out8 = {stores checked, mismatches, first mismatch (chunk << 16 | thread), carried, expected, walk step}, counters
- * reset. FEM_EARG in a normal build. */
-int fem_mf_spcheck(uint64_t* out8);
 /* out6 = {chunks, slots, bs, static bytes streamed per application, M, N} */
 int fem_mf_info(fem_mf* m, int64_t* out6);
 /* device copies of the layout (each nullable): Morton element order [M], chunk element offsets and slot offsets

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Fixed-iteration time of the persistent Poisson iteration, single-reduction vs pipelined (FEM_TUNE_PK_GV), on the
-Kuhn cube of --n (timing only; FEM355_LIB selects a build, e.g. a FEM_GV_PROBE timing build).
+Kuhn cube of --n (timing only).
 
     python tools/gv_probe.py --n 55 --iters 500
 """

@@ -1,7 +1,7 @@
 """Element stiffness / mass kernel timing on the BASELINE configs[4] families (c3d8 88^3, c3d6 2*70^3, c3d10 6*48^3,
 jittered): best of 5 event-timed calls of compute_K_matrix / compute_M_matrix after a warm-up, output write GB/s,
 and a checksum of the element matrices (build variants must agree bit for bit). Select a library build with
-FEM355_LIB=... (tools/build_variants.sh).
+FEM355_LIB=...
 
     python tools/iso_ke_probe.py
 """

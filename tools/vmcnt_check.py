@@ -2,7 +2,7 @@
 """Straight-line check of an AMDGPU kernel's ISA (hipcc --save-temps .s) for reads of VGPRs whose vector-memory
 load may still be in flight: walks the loop body from its header to the back edge in layout order (every block taken,
 loads retire in issue order, `s_waitcnt vmcnt(N)` leaves the N youngest outstanding) and reports each instruction
-that reads a pending load's destination. Diagnostic for VERDICT r04 item 2 (tools/mf_spcheck.py).
+that reads a pending load's destination. Diagnostic for VERDICT r04 item 2.
 
     python tools/vmcnt_check.py FILE.s KERNEL_SYMBOL"""
 import re
