@@ -179,6 +179,12 @@ SIGNATURES = {
     "fem_pcg_dist_phase": (_I, [_P, _I]),
     "fem_pcg_dist_buffer": (_I, [_P, _I, ctypes.POINTER(_P), ctypes.POINTER(_L)]),
     "fem_group_allreduce": (_I, [_P, _I, _L, _P]),
+    "fem_spmm": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "fem_mpcg_create": (_I, [_L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, ctypes.POINTER(_D), _D, _P, _L, _P,
+                             ctypes.POINTER(_P)]),
+    "fem_mpcg_solve": (_I, [_P, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_D)]),
+    "fem_mpcg_scalars": (_I, [_P, ctypes.POINTER(_D)]),
+    "fem_mpcg_destroy": (None, [_P]),
 }
 
 _lib = None

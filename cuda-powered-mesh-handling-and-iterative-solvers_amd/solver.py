@@ -173,6 +173,14 @@ def new_constrained_conjugate_gradient_solver(K, elements, N, rbe2_list, rbe3_li
 
 
 # ============================================================================ PCG (`solver/solver.py:766-833`)
+def _pcg_messages(res):
+    """`solver/solver.py:805-811`."""
+    if res.status == C.PCG_CONVERGED:
+        print(f"Converged after {res.iterations} iterations.")
+    else:
+        print("Preconditioned CG did not converge within the maximum number of iterations.")
+
+
 def preconditioned_conjugate_gradient_solver(K, elements, F, M_inv, u_init=None, tol=1e-8, max_iter=1000,
                                              device="cuda:0", dtype=torch.float32, return_info=False):
     """Jacobi-PCG: z = M_inv r, stop when sqrt(r.z) < tol (absolute), no eps and no breakdown guards; fixed DOFs
@@ -184,10 +192,7 @@ def preconditioned_conjugate_gradient_solver(K, elements, F, M_inv, u_init=None,
     w = M_inv.to(device=dev, dtype=F64).reshape(-1)
     b = F.to(device=dev, dtype=F64).reshape(-1)
     res = A.pcg(b, u_init, w=w, mode=C.MODE_PCG, tol=tol, max_iter=max_iter)
-    if res.status == C.PCG_CONVERGED:
-        print(f"Converged after {res.iterations} iterations.")
-    else:
-        print("Preconditioned CG did not converge within the maximum number of iterations.")
+    _pcg_messages(res)
     u = res.x.view(N, A.bs).to(device=torch.device(device), dtype=dtype)
     return (u, res) if return_info else u
 
@@ -300,6 +305,128 @@ def solve_tet4(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, tol=1e
     if inv is not None:
         u = u[inv]
     return u, res, A
+
+
+# ============================================================================ several load cases per matrix
+# The structural cases come with several load cases per part (the notebooks' SimJEB `forces` sets), and the reference
+# applies K to several vectors by looping `compute_nodal_forces` over them (`solver/solver.py:1151-1168,1207-1216`).
+# These solvers run the load cases in lock-step on one assembled matrix (SellMatrix.pcg_multi): the matrix is read once
+# per iteration for all load cases of a pass. Each load case is the CG / PCG of the single solver above and prints its message.
+def _check_loads(what, F, n_nodes_min, dpn, u_init):
+    """ValueError for a load set that does not fit the mesh -- before any device call."""
+    if F.dim() != 3:
+        raise ValueError(f"{what}: F must be [L, N, dpn] (one [N, dpn] load per case), got {tuple(F.shape)}")
+    L, N, d = F.shape
+    if L < 1:
+        raise ValueError(f"{what}: no load case (F is {tuple(F.shape)})")
+    if d != dpn:
+        raise ValueError(f"{what}: F is [L, N, {d}] but the operator has {dpn} dofs per node")
+    if N < n_nodes_min:
+        raise ValueError(f"{what}: F has {N} nodes but the mesh references node {n_nodes_min - 1}")
+    if u_init is not None and tuple(u_init.shape) != (L, N, d):
+        raise ValueError(f"{what}: u_init must be {(L, N, d)} like F, got {tuple(u_init.shape)}")
+    return L, N
+
+
+def _ke_dpn(what, K, elements):
+    if K.dim() != 3 or elements.dim() != 2 or K.shape[-1] % elements.shape[1]:
+        raise ValueError(f"{what}: K {tuple(K.shape)} does not fit elements {tuple(elements.shape)}")
+    return K.shape[-1] // elements.shape[1]
+
+
+def _max_node(elements):
+    return int(elements.max()) + 1 if elements.numel() else 0
+
+
+def _to_columns(F, dev):
+    """[L, N, dpn] -> the kernels' [N * dpn, L] (the L values of one dof adjacent)."""
+    L, N, d = F.shape
+    return F.to(device=dev, dtype=F64).permute(1, 2, 0).reshape(N * d, L).contiguous()
+
+
+def _from_columns(x, N, dpn):
+    return x.view(N, dpn, -1).permute(2, 0, 1).contiguous()
+
+
+def _prefixed(prefix, messages, *args):
+    """Print what `messages(*args)` prints, led by `prefix`."""
+    import contextlib
+    import io
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        messages(*args)
+    print(prefix + buf.getvalue(), end="")
+
+
+def multi_load_cg_solver(K, elements, F, rbe2, u_init=None, tol=1e-10, max_iter=1000, device="cuda:0",
+                         dtype=torch.float64, eps=1e-30, return_info=False):
+    """`stable_conjugate_gradient_solver` for L load cases F [L, N, dpn] on one matrix, solved in lock-step; the nodes
+    `rbe2` are held at zero in every case. `tol` is a float or one value per load case. Prints, per load case in
+    order, the single solver's message led by "Load case j: ". Returns u [L, N, dpn] (with return_info also the
+    MultiPcgResult)."""
+    what = "multi_load_cg_solver"
+    dpn = _ke_dpn(what, K, elements)
+    L, N = _check_loads(what, F, _max_node(elements), dpn, u_init)
+    dev = _dev(device)
+    A = assemble(K, elements, N, dev)
+    w = _free_mask(N, A.bs, rbe2, dev)
+    x0 = None if u_init is None else _to_columns(u_init, dev)
+    res = A.pcg_multi(_to_columns(F, dev), x0, w=w, mode=C.MODE_CG_STABLE, tol=tol, max_iter=max_iter, eps=eps)
+    for j in range(L):
+        _prefixed(f"Load case {j}: ", _cg_messages, res.column(j), "stable")
+    u = _from_columns(res.x, N, A.bs).to(device=torch.device(device), dtype=dtype)
+    return (u, res) if return_info else u
+
+
+def multi_load_pcg_solver(K, elements, F, M_inv, u_init=None, tol=1e-8, max_iter=1000, device="cuda:0",
+                          dtype=torch.float32, return_info=False):
+    """`preconditioned_conjugate_gradient_solver` for L load cases F [L, N, dpn] on one matrix and one M_inv [N, dpn],
+    solved in lock-step (fp64 arithmetic whatever `dtype`, as the single solver). `tol` is a float or one value per
+    load case. Prints, per load case in order, the single solver's message led by "Load case j: ". Returns
+    u [L, N, dpn] (with return_info also the MultiPcgResult)."""
+    what = "multi_load_pcg_solver"
+    dpn = _ke_dpn(what, K, elements)
+    L, N = _check_loads(what, F, _max_node(elements), dpn, u_init)
+    if M_inv.numel() != N * dpn:
+        raise ValueError(f"{what}: M_inv must be [{N}, {dpn}], got {tuple(M_inv.shape)}")
+    dev = _dev(device)
+    A = assemble(K, elements, N, dev)
+    w = M_inv.to(device=dev, dtype=F64).reshape(-1)
+    x0 = None if u_init is None else _to_columns(u_init, dev)
+    res = A.pcg_multi(_to_columns(F, dev), x0, w=w, mode=C.MODE_PCG, tol=tol, max_iter=max_iter)
+    for j in range(L):
+        _prefixed(f"Load case {j}: ", _pcg_messages, res.column(j))
+    u = _from_columns(res.x, N, A.bs).to(device=torch.device(device), dtype=dtype)
+    return (u, res) if return_info else u
+
+
+def solve_tet4_multi(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, tol=1e-8, max_iter=10000,
+                     device="cuda:0", rtol=None):
+    """`solve_tet4` for L load cases f [L, N, dpn] (assembled operator only): one assembly, one exact Jacobi M_inv with
+    zeros on the `fixed` nodes, the load cases solved in lock-step. `rtol` scales each load case's tolerance by its
+    own sqrt(r0.z0). Returns (u [L, N, dpn], MultiPcgResult, SellMatrix)."""
+    what = "solve_tet4_multi"
+    if kind not in ("poisson", "elastic"):
+        raise ValueError(f"{what}: unknown kind {kind!r} ('poisson' or 'elastic')")
+    dpn = 1 if kind == "poisson" else 3
+    if coords.dim() != 2 or coords.shape[1] != 3:
+        raise ValueError(f"{what}: coords must be [N, 3], got {tuple(coords.shape)}")
+    L, N = _check_loads(what, f, max(_max_node(elements), coords.shape[0]), dpn, None)
+    if N != coords.shape[0]:
+        raise ValueError(f"{what}: f has {N} nodes but coords {coords.shape[0]}")
+    dev = _dev(device)
+    coords = coords.to(device=dev, dtype=F64).contiguous()
+    elements = elements.to(device=dev, dtype=LONG).contiguous()
+    A = _sys.assemble_tet4_system(coords, elements, kind, E, nu)
+    A.check_singular()
+    mask = torch.zeros((N, A.bs), dtype=torch.uint8, device=dev)
+    mask[torch.as_tensor(fixed).to(device=dev)] = 1
+    w = A.jacobi(mask.view(-1))
+    B = _to_columns(f, dev)
+    if rtol is not None:
+        tol = [float(rtol) * float(t) for t in torch.sqrt((B * (w[:, None] * B)).sum(0)).cpu()]
+    res = A.pcg_multi(B, None, w=w, mode=C.MODE_PCG, tol=tol, max_iter=max_iter)
+    return _from_columns(res.x, N, A.bs), res, A
 
 # every public function runs in the scope of the device its `device` argument names (_capi.on_device)
 C.scope_module(globals())

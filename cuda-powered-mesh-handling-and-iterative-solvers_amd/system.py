@@ -77,6 +77,49 @@ class PcgResult:
     schedule: int = -1   # the kernel schedule the solve ran (SCHED_*; after any fallback)
 
 
+# multi-load-case kernels (csrc/pcg_multi.hip): the column counts they are built for, and the most columns one pass
+# takes per block size. bs = 3 runs in passes of 4: measured on the 10M-tet elastic matrix, the 8-column SpMM takes
+# 1514 us against 2 x 489 us for two 4-column ones (its gather window of 192 bytes per block column no longer fits the
+# L2 of an XCD; DESIGN.md, profiles/multi_rhs_n119_wide8.json). `max_cols=8` selects the wide pass all the same.
+MULTI_NV = (2, 4, 8)
+MULTI_MAX = {1: 8, 3: 4}
+
+
+def multi_passes(L: int, bs: int = 1, max_cols: int = None):
+    """Split L right-hand sides into lock-step passes: [(first column, columns, NV)] with at most `max_cols` columns
+    per pass (default MULTI_MAX[bs]) and NV the next instantiated column count (the pass is padded with NV - columns
+    zero columns): 11 -> [(0, 8, 8), (8, 3, 4)] for bs = 1, [(0, 4, 4), (4, 4, 4), (8, 3, 4)] for bs = 3."""
+    if L < 1:
+        raise ValueError(f"at least one right-hand side is needed, got {L}")
+    width = MULTI_MAX.get(bs, MULTI_NV[-1]) if max_cols is None else int(max_cols)
+    if not 1 <= width <= MULTI_NV[-1]:
+        raise ValueError(f"a pass takes 1 to {MULTI_NV[-1]} columns, got {width}")
+    out, j = [], 0
+    while j < L:
+        k = min(width, L - j)
+        out.append((j, k, next(v for v in MULTI_NV if v >= k)))
+        j += k
+    return out
+
+
+@dataclass
+class MultiPcgResult:
+    """SellMatrix.pcg_multi: the PcgResult fields per load case (column j of x, entry j of the lists)."""
+    x: torch.Tensor          # [n, L]
+    iterations: list         # [L] the reference's reported count per column
+    status: list             # [L] _capi.PCG_*
+    rz: list                 # [L] last r.z (r.r in CG mode)
+    pq: list                 # [L] last p.Ap
+    history: torch.Tensor = None   # [max(iterations), L]; rows past a column's own stop are NaN
+
+    def column(self, j: int) -> PcgResult:
+        """Load case j as the PcgResult a single solve returns."""
+        hist = None
+        if self.history is not None:
+            hist = self.history[: min(self.iterations[j], self.history.shape[0]), j]
+        return PcgResult(self.x[:, j], self.iterations[j], self.status[j], self.rz[j], self.pq[j], hist)
+
+
 @dataclass
 class Graph:
     """Node graph of a mesh: incidence + CSR pattern + SELL-64 pattern, all on one device."""
@@ -661,6 +704,99 @@ class SellMatrix:
         if hist is not None:
             hist = hist[: min(it.value, hist.numel())]
         return PcgResult(x, it.value, stt.value, rz.value, sc[1], hist, ran)
+
+    # ---------------------------------------------------------------- several right-hand sides
+    def _multi_cols(self):
+        """(cols, dcols) arguments of the multi-vector kernels: the 16-bit deltas when the graph has them."""
+        return C.ptr(self.g.cols), (C.ptr(self.g.dcols) if self.use16 else None)
+
+    def matvec_multi(self, X: torch.Tensor, max_cols: int = None):
+        """Y = A X for X [n, L], any L >= 1: the matrix is streamed once per pass (multi_passes: up to 8 columns for
+        bs = 1, 4 for bs = 3; `max_cols` overrides) (include/fem355.h fem_spmm) instead of once per column. Column j
+        equals matvec(X[:, j]) up to FMA contraction.
+        Reads the plain SELL values: for a matrix held in the solver layout `plain_values()` forms a plain copy once,
+        so one extra resident copy of the values."""
+        if X.dim() != 2 or X.shape[0] != self.n or X.shape[1] < 1:
+            raise ValueError(f"matvec_multi: X must be [{self.n}, L] with L >= 1, got {tuple(X.shape)}")
+        lib = C.lib()
+        X = X.to(device=self.device, dtype=F64)
+        L = X.shape[1]
+        Y = torch.empty((self.n, L), dtype=F64, device=self.device)
+        cols, dcols = self._multi_cols()
+        vals = C.ptr(self.plain_values())
+        for j, k, nv in multi_passes(L, self.bs, max_cols):
+            if k == nv == L and X.is_contiguous() and X.data_ptr() % 16 == 0:
+                Xp, Yp = X, Y
+            else:
+                Xp = torch.zeros((self.n, nv), dtype=F64, device=self.device)
+                Xp[:, :k] = X[:, j:j + k]
+                Yp = torch.empty((self.n, nv), dtype=F64, device=self.device)
+            C.check(lib.fem_spmm(self.g.n_nodes, self.bs, nv, C.ptr(self.g.slice_ptr), cols, dcols, vals, C.ptr(Xp),
+                                 C.ptr(Yp), C.stream(self.device)), "fem_spmm")
+            if Yp is not Y:
+                Y[:, j:j + k] = Yp[:, :k]
+        return Y
+
+    def pcg_multi(self, B, x0=None, w=None, mode=C.MODE_PCG, tol=1e-8, max_iter=1000, eps=1e-30, history=False,
+                  chunk=32, max_cols=None):
+        """The device (P)CG for L right-hand sides B [n, L] in lock-step (include/fem355.h fem_mpcg_*): every column
+        is the CG / Jacobi-PCG of `pcg` with its own alpha, beta, iteration count and status, and the matrix is read
+        once per iteration for all columns of a pass; more columns than a pass takes (multi_passes: 8 for bs = 1, 4
+        for bs = 3; `max_cols` overrides, at most 8) run in several passes. `w` [n] is shared by all columns,
+        `tol` is a float or a length-L sequence. A column that has stopped is frozen; the others go on. Modes
+        MODE_PCG and MODE_CG_STABLE. Returns a MultiPcgResult. Plain launches only, so no status needs the
+        synchronisation check of `pcg`.
+        Reads the plain SELL values: for a matrix held in the solver layout `plain_values()` forms a plain copy once,
+        so one extra resident copy of the values."""
+        if B.dim() != 2 or B.shape[0] != self.n or B.shape[1] < 1:
+            raise ValueError(f"pcg_multi: B must be [{self.n}, L] with L >= 1, got {tuple(B.shape)}")
+        L = B.shape[1]
+        if x0 is not None and tuple(x0.shape) != (self.n, L):
+            raise ValueError(f"pcg_multi: x0 must be [{self.n}, {L}], got {tuple(x0.shape)}")
+        if w is None or w.numel() != self.n:
+            raise ValueError(f"pcg_multi: w must hold {self.n} values (shared by all columns)")
+        tols = [float(tol)] * L if not hasattr(tol, "__len__") else [float(t) for t in tol]
+        if len(tols) != L:
+            raise ValueError(f"pcg_multi: {len(tols)} tolerances for {L} columns")
+        lib = C.lib()
+        B = B.to(device=self.device, dtype=F64)
+        w = w.to(device=self.device, dtype=F64).contiguous().view(-1)
+        x = torch.zeros((self.n, L), dtype=F64, device=self.device)
+        cols, dcols = self._multi_cols()
+        vals = C.ptr(self.plain_values())
+        its, stts, rzs, pqs, hists = [], [], [], [], []
+        for j, k, nv in multi_passes(L, self.bs, max_cols):
+            Bp = torch.zeros((self.n, nv), dtype=F64, device=self.device)
+            Bp[:, :k] = B[:, j:j + k]
+            Xp = torch.zeros((self.n, nv), dtype=F64, device=self.device)
+            if x0 is not None:
+                Xp[:, :k] = x0[:, j:j + k].to(device=self.device, dtype=F64)
+            hist = (torch.full((max(max_iter, 1), nv), float("nan"), dtype=F64, device=self.device)
+                    if history else None)
+            tl = (ctypes.c_double * nv)(*tols[j:j + k])
+            h = ctypes.c_void_p()
+            C.check(lib.fem_mpcg_create(self.g.n_nodes, self.bs, nv, k, C.ptr(self.g.slice_ptr), cols, dcols, vals,
+                                        C.ptr(Bp), C.ptr(Xp), C.ptr(w), int(mode), tl, float(eps), C.ptr(hist),
+                                        hist.shape[0] if hist is not None else 0, C.stream(self.device),
+                                        ctypes.byref(h)), "fem_mpcg_create")
+            try:
+                it, stt, rz = (ctypes.c_int * nv)(), (ctypes.c_int * nv)(), (ctypes.c_double * nv)()
+                C.check(lib.fem_mpcg_solve(h, int(max_iter), int(chunk), it, stt, rz), "fem_mpcg_solve")
+                sc = (ctypes.c_double * (6 * nv))()
+                C.check(lib.fem_mpcg_scalars(h, sc), "fem_mpcg_scalars")
+            finally:
+                lib.fem_mpcg_destroy(h)
+            x[:, j:j + k] = Xp[:, :k]
+            its += list(it[:k])
+            stts += list(stt[:k])
+            rzs += list(rz[:k])
+            pqs += [sc[6 * v + 1] for v in range(k)]
+            if hist is not None:
+                hists.append(hist[:, :k])
+        hist = None
+        if history:
+            hist = torch.cat(hists, dim=1)[: min(max(its), max(max_iter, 1))]
+        return MultiPcgResult(x, its, stts, rzs, pqs, hist)
 
 
 @_scoped

@@ -741,6 +741,39 @@ int fem_mf_order(fem_mf* m, int32_t* eorder, int32_t* cptr, int32_t* sbase, int3
  * per partition, `subdivision.ipynb:248-279`). */
 int fem_pcg_set_operator_mf(fem_pcg* s, fem_mf* m);
 
+/* ------------------------------------------------------------------ multi-load-case (P)CG (csrc/pcg_multi.hip)
+ * Several right-hand sides of one matrix solved in lock-step: the matrix is streamed once per iteration for all of
+ * them. Multi-vectors are [n, nv] row-major (n = nrows * bs; the nv columns of one dof adjacent, 16-byte aligned);
+ * nv is 2, 4 or 8 (the caller pads with zero columns), bs 1 or 3; anything else is FEM_EARG. The matrix is the plain
+ * SELL-64 layout at the top of this file, columns as 16-bit deltas dcols (column = row + delta) when not NULL, else
+ * the int32 cols.
+ * fem_spmm: Y = A X (the reference applies K to several vectors by looping `compute_nodal_forces` over them,
+ *   `solver/solver.py:1151-1168`), per row and column the summation order of fem_spmv. */
+int fem_spmm(int64_t nrows, int bs, int nv, const int64_t* slice_ptr, const int32_t* cols, const int16_t* dcols,
+             const double* vals, const double* X, double* Y, fem_stream_t stream);
+/* One context for nv columns of which the first nactive are solved; the rest are padding, frozen from the start,
+ * never updated and never reported (their B and X columns must be zero). B, X [n, nv]; w [n] is shared by all columns
+ * (one matrix, one fixed set); tol [host, nv] is per column; hist [hist_len, nv] (may be NULL) receives sqrt(r.z)
+ * (sqrt(r.r) for CG) per iteration and column. Modes FEM_MODE_CG_STABLE and FEM_MODE_PCG, column by column with
+ * exactly the semantics documented at fem_pcg_create (mask and eps, the three CG guards reporting the reference's
+ * printed iteration, no guards in PCG mode, stop on sqrt(r.r) resp. sqrt(r.z) < tol[j]); FEM_MODE_CG_CONSTRAINED is
+ * FEM_EARG. Every column has its own alpha, beta, iteration count and status on the device; a column that has
+ * stopped is frozen (x, r, p skipped by predicate), so a breakdown or NaN in one column never reaches another, and
+ * a column's bits do not depend on what the other columns hold. Plain launches only; reductions are finished by a
+ * later launch in a fixed order (bit-reproducible). */
+typedef struct fem_mpcg fem_mpcg;
+int fem_mpcg_create(int64_t nrows, int bs, int nv, int nactive, const int64_t* slice_ptr, const int32_t* cols,
+                    const int16_t* dcols, const double* vals, const double* B, double* X, const double* w, int mode,
+                    const double* tol, double eps, double* hist, int64_t hist_len, fem_stream_t stream,
+                    fem_mpcg** out);
+/* [sync] run from the X in place until every active column has stopped or max_iter (columns still running then:
+ * FEM_PCG_MAXITER); the host enqueues `chunk` iterations at a time and reads the state in between. iters, status,
+ * rz: [host, nactive], as fem_pcg_poll reports them per column */
+int fem_mpcg_solve(fem_mpcg* s, int max_iter, int chunk, int* iters, int* status, double* rz);
+/* [sync] out [host, nactive * 6]: fem_pcg_scalars' six values per column */
+int fem_mpcg_scalars(fem_mpcg* s, double* out);
+void fem_mpcg_destroy(fem_mpcg* s);
+
 #ifdef __cplusplus
 }
 #endif
