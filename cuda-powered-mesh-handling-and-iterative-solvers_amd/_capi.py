@@ -31,6 +31,8 @@ TUNE_PK_GV = 16384      # persistent schedule, small bs = 1 systems: the pipelin
 TUNE_DEFAULT = 1 | 2 | 4 | 8 | 128 | TUNE_UPD1
 KIND_ELASTIC, KIND_POISSON, KIND_MASS = 0, 1, 2
 ISO_SUM, ISO_STACK, ISO_VOLUME, ISO_MASS = 0, 1, 2, 3
+MASS_SELL, MASS_DIAG = 0, 1   # include/fem355.h fem_mass_form
+MODAL_OUT_GM, MODAL_OUT_NORMS, MODAL_OUT_LEN = 576, 1152, 1168   # include/fem355.h FEM_MODAL_OUT_*
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -185,6 +187,11 @@ SIGNATURES = {
     "fem_mpcg_solve": (_I, [_P, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_D)]),
     "fem_mpcg_scalars": (_I, [_P, ctypes.POINTER(_D)]),
     "fem_mpcg_destroy": (None, [_P]),
+    "fem_spmm_km": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "fem_modal_work_len": (_L, []),
+    "fem_modal_gram": (_I, [_L, _I, _I, ctypes.POINTER(_P), _P, _P, _P]),
+    "fem_modal_residual": (_I, [_L, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fem_modal_rotate": (_I, [_L, _I, _I, ctypes.POINTER(_P), _P, _P]),
 }
 
 _lib = None

@@ -428,5 +428,117 @@ def solve_tet4_multi(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, 
     res = A.pcg_multi(B, None, w=w, mode=C.MODE_PCG, tol=tol, max_iter=max_iter)
     return _from_columns(res.x, N, A.bs), res, A
 
+
+# ============================================================================ modal analysis (`solver/solver.py:1084-1313`)
+# The reference's routine iterates M^-1 K forward from torch.randn, orthonormalises in the Euclidean norm and solves
+# the small problem with 30 Jacobi rotations on a non-symmetric matrix: it drifts to the LARGEST eigenvalues although
+# its docstring promises the smallest. These solvers deliver what the docstring promises -- the lowest eigenpairs of the
+# clamped structure, M-orthonormal -- by block LOBPCG on the assembled matrices (SellMatrix.eig_lowest, csrc/modal.hip);
+# parity is pinned against a dense generalised eigensolve, not against the reference's iterates.
+def _check_modal(what, K, M, elements, num_nodes, k, mass_dims):
+    """ValueError for element matrices that do not fit the mesh -- before any device call. Returns dofs per node."""
+    dpn = _ke_dpn(what, K, elements)
+    if dpn not in (1, 3):
+        raise ValueError(f"{what}: {dpn} dofs per node unsupported (1 or 3)")
+    npe = elements.shape[1]
+    if K.shape[0] != elements.shape[0] or K.shape[1] != K.shape[2]:
+        raise ValueError(f"{what}: K {tuple(K.shape)} does not fit elements {tuple(elements.shape)}")
+    if M.dim() != 3 or M.shape[0] != elements.shape[0] or M.shape[1] != M.shape[2] or \
+            M.shape[1] not in [npe * d for d in mass_dims(dpn)]:
+        raise ValueError(f"{what}: M {tuple(M.shape)} does not fit elements {tuple(elements.shape)} "
+                         f"with {dpn} dofs per node")
+    if not 1 <= int(k) <= 8:
+        raise ValueError(f"{what}: 1 to 8 eigenpairs per solve, got {k}")
+    if _max_node(elements) > num_nodes:
+        raise ValueError(f"{what}: the mesh references node {_max_node(elements) - 1} but num_nodes is {num_nodes}")
+    return dpn
+
+
+def _fixed_ids(what, fixed, num_nodes):
+    ids = torch.as_tensor(fixed).to(LONG).reshape(-1)
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= num_nodes):
+        raise ValueError(f"{what}: a fixed node lies outside [0, {num_nodes})")
+    return ids
+
+
+def _jacobi_weights(A, ids, dev):
+    mask = torch.zeros((A.g.n_nodes, A.bs), dtype=torch.uint8, device=dev)
+    mask[ids.to(dev)] = 1
+    return A.jacobi(mask.view(-1))
+
+
+def vectorized_modal_solver(K_local, M_local, elements, rbe2_node_ids, num_nodes, num_eigs=5, max_iter=20,
+                            device="cuda:0", dtype=torch.float32, tol=1e-8, return_info=False):
+    """The `num_eigs` lowest eigenpairs of K u = lambda M u with the nodes `rbe2_node_ids` clamped: signature and
+    returns of the reference (`solver/solver.py:1084-1313`: lam [num_eigs], modes [3 num_nodes, num_eigs], in `dtype`),
+    fp64 arithmetic. The mass is lumped the reference's way -- the sum of the element matrices' diagonals, clamped at
+    1e-12 (`:1126-1134`) -- and applied as a diagonal. `max_iter` caps the LOBPCG iterations; when it is hit one line
+    `Modal solver: reached max_iter (N) with residual R` is printed and the current Ritz pairs are returned. The
+    modes are M-orthonormal with zeros on the clamped dofs. A free-free structure (nothing clamped) is out of scope:
+    the solve stops with PCG_BREAKDOWN (see SellMatrix.eig_lowest). With return_info also the ModalResult."""
+    what = "vectorized_modal_solver"
+    dpn = _check_modal(what, K_local, M_local, elements, num_nodes, num_eigs, lambda d: (d,))
+    if dpn != 3:
+        raise ValueError(f"{what}: 3 dofs per node (the reference's layout), got {dpn}")
+    ids = _fixed_ids(what, rbe2_node_ids, num_nodes)
+    dev = _dev(device)
+    A = assemble(K_local, elements, num_nodes, dev)
+    el = elements.to(device=dev, dtype=LONG)
+    dofs = (el.unsqueeze(-1) * 3 + torch.arange(3, device=dev).view(1, 1, 3)).reshape(-1)
+    md = torch.zeros(3 * num_nodes, dtype=F64, device=dev)
+    md.index_add_(0, dofs, M_local.to(device=dev, dtype=F64).diagonal(dim1=1, dim2=2).reshape(-1))
+    md.clamp_(min=1e-12)
+    res = A.eig_lowest(md, int(num_eigs), _jacobi_weights(A, ids, dev), tol=tol, max_iter=max_iter)
+    if res.status == C.PCG_MAXITER:
+        print(f"Modal solver: reached max_iter ({max_iter}) with residual {float(res.residuals.max()):.3e}")
+    elif res.status == C.PCG_BREAKDOWN:
+        print(f"Modal solver: breakdown at iteration {res.iterations} (K is not positive definite on the free dofs)")
+    lam = res.lam.to(device=torch.device(device), dtype=dtype)
+    modes = res.X.to(device=torch.device(device), dtype=dtype)
+    return (lam, modes, res) if return_info else (lam, modes)
+
+
+def modal_solver(K, M, elements, fixed, num_nodes, num_modes=6, tol=1e-8, max_iter=2000, block=None, seed=0,
+                 device="cuda:0", dtype=torch.float64, return_info=False):
+    """Natural frequencies with the consistent mass: the `num_modes` lowest eigenpairs of K u = lambda M u with the
+    nodes `fixed` clamped. K [Me, d, d] (d = dpn npe, dpn 1 or 3); M is the scalar factor [Me, npe, npe]
+    (compute_M_matrix(..., scalar=True)) or the full [Me, dpn npe, dpn npe] of compute_c3d4_M_matrix / compute_M_matrix,
+    from which the factor M[:, ::dpn, ::dpn] is taken. Both matrices are assembled on one cached graph. Returns
+    (freq_hz = sqrt(lam) / 2 pi [num_modes], lam [num_modes], modes [num_modes, N, dpn]) in `dtype` and prints one
+    line per mode; with return_info also the ModalResult."""
+    what = "modal_solver"
+    dpn = _check_modal(what, K, M, elements, num_nodes, num_modes, lambda d: (1, d))
+    ids = _fixed_ids(what, fixed, num_nodes)
+    _sys.modal_block(num_modes, block)
+    dev = _dev(device)
+    el = elements.to(device=dev, dtype=LONG).contiguous()
+    npe = el.shape[1]
+    Ke = K.to(device=dev, dtype=F64).contiguous()
+    Ms = M.to(device=dev, dtype=F64)
+    if Ms.shape[1] != npe:
+        Ms = Ms[:, ::dpn, ::dpn]
+    Ms = Ms.contiguous()
+    g = cached_graph(el, num_nodes)
+    A, Mg = _sys.SellMatrix(g, dpn), _sys.SellMatrix(g, 1)
+    if dpn == 3:
+        A.add_stiffness_and_mass(Ke, Ms, el, Mg)
+    else:
+        A.add_element_matrices(Ke, el)
+        Mg.add_element_matrices(Ms, el)
+    res = A.eig_lowest(Mg, int(num_modes), _jacobi_weights(A, ids, dev), block=block, tol=tol, max_iter=max_iter,
+                       seed=seed)
+    if res.status == C.PCG_MAXITER:
+        print(f"Modal solver: reached max_iter ({max_iter}) with residual {float(res.residuals.max()):.3e}")
+    elif res.status == C.PCG_BREAKDOWN:
+        print(f"Modal solver: breakdown at iteration {res.iterations} (K is not positive definite on the free dofs)")
+    freq = torch.sqrt(res.lam.clamp(min=0.0)) / (2.0 * torch.pi)
+    for j in range(int(num_modes)):
+        print(f"Mode {j + 1}: f = {float(freq[j]):.6e} Hz, lambda = {float(res.lam[j]):.6e}, "
+              f"residual {float(res.residuals[j]):.3e}")
+    out = torch.device(device)
+    modes = res.X.T.reshape(int(num_modes), num_nodes, dpn)
+    ret = (freq.to(device=out, dtype=dtype), res.lam.to(device=out, dtype=dtype), modes.to(device=out, dtype=dtype))
+    return ret + (res,) if return_info else ret
+
 # every public function runs in the scope of the device its `device` argument names (_capi.on_device)
 C.scope_module(globals())

@@ -121,6 +121,64 @@ class MultiPcgResult:
 
 
 @dataclass
+class ModalResult:
+    """SellMatrix.eig_lowest: the k lowest eigenpairs of K u = lambda M u on the free dofs."""
+    lam: torch.Tensor              # [k] ascending (host, fp64)
+    X: torch.Tensor                # [n, k] M-orthonormal, zeros on the fixed dofs (device)
+    iterations: int                # LOBPCG iterations (rotations of the basis) made
+    status: int                    # _capi.PCG_CONVERGED / PCG_MAXITER / PCG_BREAKDOWN
+    residuals: torch.Tensor        # [k] ||K x - lam M x|| / (lam ||M x||) over the free dofs, as last measured
+    restarts: int = 0              # iterations whose Rayleigh-Ritz dropped P
+    history: torch.Tensor = None   # [iterations, k]: the residuals after every iteration
+
+
+# Rayleigh-Ritz guards of the block LOBPCG. MODAL_COND: the scaled Gram matrix of the mass is dropped to [X W] past
+# this eigh condition number. MODAL_THETA_FLOOR: a Ritz value at or below this fraction of the largest Ritz value of
+# the start block (a lower bound of lambda_max) means lambda_1 / lambda_max < 1e-12 -- the rounding of a residual,
+# eps * lambda_max / lambda_1 > 1e-4, then lies far above any usable tolerance, and a clamped structure's K is
+# positive definite with a ratio of the order of (h / L)^2: the matrix is singular (no clamped dof) -> breakdown.
+MODAL_COND = 1e12
+MODAL_THETA_FLOOR = 1e-12
+
+
+def modal_block(k: int, block: int = None) -> int:
+    """Block width m of the LOBPCG for k eigenpairs: the smallest multi-vector width (MULTI_NV) that is >= k + 2,
+    capped at 8; `block` (k <= block <= 8) is rounded up to such a width instead."""
+    if not 1 <= int(k) <= MULTI_NV[-1]:
+        raise ValueError(f"eig_lowest: 1 to {MULTI_NV[-1]} eigenpairs per solve, got {k}")
+    want = min(int(k) + 2, MULTI_NV[-1]) if block is None else int(block)
+    if not int(k) <= want <= MULTI_NV[-1]:
+        raise ValueError(f"eig_lowest: block must lie in [{k}, {MULTI_NV[-1]}], got {block}")
+    return next(v for v in MULTI_NV if v >= want)
+
+
+def rayleigh_ritz(GK: torch.Tensor, GM: torch.Tensor, m: int):
+    """The m lowest Ritz pairs of the small pencil (GK, GM) on the host: both scaled by diag(GM)^(-1/2), GM
+    Cholesky-factored, the standard symmetric problem solved by eigh. Returns (theta [m], C [am, m]) with
+    C^T GM C = I, or None when GM is not safely positive definite (non-finite entries, a diagonal <= 0, a failed
+    Cholesky, or an eigh condition number of the scaled GM above MODAL_COND)."""
+    GK, GM = GK.to(F64), GM.to(F64)
+    d = GM.diagonal()
+    if not bool(torch.isfinite(GK).all() and torch.isfinite(GM).all()) or bool((d <= 0).any()):
+        return None
+    s = d.rsqrt()
+    A = s[:, None] * GK * s[None, :]
+    B = s[:, None] * GM * s[None, :]
+    ev = torch.linalg.eigvalsh(B)
+    if not float(ev[0]) > 0.0 or float(ev[-1] / ev[0]) > MODAL_COND:
+        return None
+    L, info = torch.linalg.cholesky_ex(B)
+    if int(info) != 0:
+        return None
+    T = torch.linalg.solve_triangular(L, A, upper=False)                 # L^-1 A
+    T = torch.linalg.solve_triangular(L, T.T.contiguous(), upper=False)  # L^-1 A L^-T (transposed: symmetric)
+    T = 0.5 * (T + T.T)
+    lam, Z = torch.linalg.eigh(T)
+    Cm = s[:, None] * torch.linalg.solve_triangular(L.T.contiguous(), Z[:, :m].contiguous(), upper=True)
+    return lam[:m].clone(), Cm.contiguous()
+
+
+@dataclass
 class Graph:
     """Node graph of a mesh: incidence + CSR pattern + SELL-64 pattern, all on one device."""
     n_nodes: int
@@ -797,6 +855,173 @@ class SellMatrix:
         if history:
             hist = torch.cat(hists, dim=1)[: min(max(its), max(max_iter, 1))]
         return MultiPcgResult(x, its, stts, rzs, pqs, hist)
+
+    # ---------------------------------------------------------------- stiffness and mass together
+    def _mass_form(self, what, mass):
+        """(FEM_MASS_* form, mass) of a `mass` argument, ValueError for one that does not fit -- no device call."""
+        if isinstance(mass, SellMatrix):
+            if mass.g is not self.g:
+                raise ValueError(f"{what}: the mass matrix must be assembled on the same Graph object as this matrix")
+            if mass.bs != 1:
+                raise ValueError(f"{what}: the mass matrix is the scalar factor M_s (bs = 1), got bs = {mass.bs}")
+            return C.MASS_SELL, mass
+        if not torch.is_tensor(mass) or mass.dim() != 1 or mass.numel() != self.n:
+            shape = tuple(mass.shape) if torch.is_tensor(mass) else type(mass).__name__
+            raise ValueError(f"{what}: mass must be a bs = 1 SellMatrix or a diagonal of length {self.n}, got {shape}")
+        return C.MASS_DIAG, mass
+
+    def _mass_values(self, form, mass):
+        if form == C.MASS_SELL:
+            return mass.plain_values()
+        return mass.to(device=self.device, dtype=F64).contiguous()
+
+    def matvec_km_multi(self, mass, X: torch.Tensor, max_cols: int = None):
+        """(K X, M X) for X [n, L] in one sweep of the pattern per pass (include/fem355.h fem_spmm_km): every gathered
+        block column of X is loaded once for both products. `mass` is a bs = 1 SellMatrix on the same Graph object
+        (M = M_s (x) I_bs: what add_stiffness_and_mass / compute_M_matrix(..., scalar=True) produce) or a tensor [n]
+        (M = diag(mass)). Passes and padding as matvec_multi; column j of K X equals matvec_multi's bit for bit."""
+        form, mass = self._mass_form("matvec_km_multi", mass)
+        if X.dim() != 2 or X.shape[0] != self.n or X.shape[1] < 1:
+            raise ValueError(f"matvec_km_multi: X must be [{self.n}, L] with L >= 1, got {tuple(X.shape)}")
+        passes = multi_passes(X.shape[1], self.bs, max_cols)
+        lib = C.lib()
+        X = X.to(device=self.device, dtype=F64)
+        L = X.shape[1]
+        Y = torch.empty((self.n, L), dtype=F64, device=self.device)
+        Z = torch.empty((self.n, L), dtype=F64, device=self.device)
+        cols, dcols = self._multi_cols()
+        vals, mv = self.plain_values(), self._mass_values(form, mass)
+        for j, k, nv in passes:
+            if k == nv == L and X.is_contiguous() and X.data_ptr() % 16 == 0:
+                Xp, Yp, Zp = X, Y, Z
+            else:
+                Xp = torch.zeros((self.n, nv), dtype=F64, device=self.device)
+                Xp[:, :k] = X[:, j:j + k]
+                Yp = torch.empty((self.n, nv), dtype=F64, device=self.device)
+                Zp = torch.empty((self.n, nv), dtype=F64, device=self.device)
+            C.check(lib.fem_spmm_km(self.g.n_nodes, self.bs, nv, C.ptr(self.g.slice_ptr), cols, dcols, C.ptr(vals),
+                                    C.ptr(mv), form, C.ptr(Xp), C.ptr(Yp), C.ptr(Zp), C.stream(self.device)),
+                    "fem_spmm_km")
+            if Yp is not Y:
+                Y[:, j:j + k] = Yp[:, :k]
+                Z[:, j:j + k] = Zp[:, :k]
+        return Y, Z
+
+    def eig_lowest(self, mass, k, w, block=None, tol=1e-8, max_iter=2000, seed=0, X0=None, history=False):
+        """The k lowest eigenpairs of K u = lambda M u by block LOBPCG with the Jacobi preconditioner (csrc/modal.hip;
+        what the docstring of the reference's `vectorized_modal_solver`, `solver/solver.py:1084-1313`, promises).
+        `mass` as in matvec_km_multi. `w` [n] holds the Jacobi weights with zeros on the fixed dofs (SellMatrix.jacobi):
+        X, W and P hold zeros on those rows from the start, so the pencil is the one of the free dofs and no row is
+        eliminated. Block width m = modal_block(k, block). Per iteration: the residual R = KX - MX diag(theta) with
+        W = w o R, ONE pass over the matrix for KW and MW, the Gram matrices of [X W P], one device-to-host read of
+        them, Rayleigh-Ritz on the host (rayleigh_ritz; P is dropped for the iteration when the basis is too
+        ill-conditioned: a restart), and the rotation of the basis and its products in place. Column j has converged
+        when ||R_j|| <= tol theta_j ||MX_j|| (norms over the free dofs); the solve stops when the first k have.
+        The start block comes from torch.Generator().manual_seed(seed) on the host (X0 [n, <= m] replaces its first
+        columns) and is followed by a Rayleigh-Ritz on X alone. Same input, same bits.
+        The clamped K must be positive definite: a Ritz value that is not finite, <= 0 or below MODAL_THETA_FLOOR of
+        the start block's largest stops the solve with PCG_BREAKDOWN (the last good values are returned). Free-free
+        structures and spectral shifts are out of scope. No column locking. Returns a ModalResult."""
+        form, mass = self._mass_form("eig_lowest", mass)
+        m = modal_block(k, block)
+        k = int(k)
+        if w is None or w.numel() != self.n:
+            raise ValueError(f"eig_lowest: w must hold {self.n} values (Jacobi weights, zero on the fixed dofs)")
+        if X0 is not None and (X0.dim() != 2 or X0.shape[0] != self.n or not 1 <= X0.shape[1] <= m):
+            raise ValueError(f"eig_lowest: X0 must be [{self.n}, 1..{m}], got {tuple(X0.shape)}")
+        if max_iter < 0:
+            raise ValueError(f"eig_lowest: max_iter must be >= 0, got {max_iter}")
+        lib = C.lib()
+        dev, n = self.device, self.n
+        w = w.to(device=dev, dtype=F64).contiguous().view(-1)
+        start = torch.randn((n, m), dtype=F64, generator=torch.Generator().manual_seed(int(seed)))
+        V = [torch.zeros((n, m), dtype=F64, device=dev) for _ in range(9)]   # X W P KX KW KP MX MW MP
+        X, W, _, KX, KW, _, MX, MW, _ = V
+        X.copy_(start)
+        if X0 is not None:
+            X[:, :X0.shape[1]] = X0.to(device=dev, dtype=F64)
+        X.mul_((w != 0).to(F64)[:, None])
+        ptrs = (ctypes.c_void_p * 9)(*[v.data_ptr() for v in V])
+        work = torch.empty(int(lib.fem_modal_work_len()), dtype=F64, device=dev)
+        out = torch.zeros(C.MODAL_OUT_LEN, dtype=F64, device=dev)
+        coef = torch.zeros(3 * 64 + 8, dtype=F64, device=dev)     # C [a m, m], then theta at 192
+        coef_host = torch.zeros(3 * 64 + 8, dtype=F64)
+        cols, dcols = self._multi_cols()
+        vals, mv = self.plain_values(), self._mass_values(form, mass)
+        st = C.stream(dev)
+
+        def product(Vin, KV, MV):
+            C.check(lib.fem_spmm_km(self.g.n_nodes, self.bs, m, C.ptr(self.g.slice_ptr), cols, dcols, C.ptr(vals),
+                                    C.ptr(mv), form, C.ptr(Vin), C.ptr(KV), C.ptr(MV), st), "fem_spmm_km")
+
+        def gram(a):
+            C.check(lib.fem_modal_gram(n, m, a, ptrs, C.ptr(work), C.ptr(out), st), "fem_modal_gram")
+
+        def grams(host, a, sub):
+            """(G_K, G_M) of the leading `sub` blocks out of a Gram launch with `a` blocks."""
+            am = a * m
+            GK = host[: am * am].view(am, am)[: sub * m, : sub * m]
+            GM = host[C.MODAL_OUT_GM: C.MODAL_OUT_GM + am * am].view(am, am)[: sub * m, : sub * m]
+            return GK, GM
+
+        def rotate(a, theta, Cm):
+            coef_host.zero_()
+            coef_host[: a * m * m] = Cm.reshape(-1)
+            coef_host[192: 192 + m] = theta
+            coef.copy_(coef_host)
+            C.check(lib.fem_modal_rotate(n, m, a, ptrs, C.ptr(coef), st), "fem_modal_rotate")
+
+        def bad(theta, ref):
+            return not bool(torch.isfinite(theta).all()) or bool((theta <= MODAL_THETA_FLOOR * ref).any())
+
+        def result(theta, status, it, rel, restarts, hist):
+            h = torch.stack(hist[1:]) if len(hist) > 1 else torch.zeros((0, k), dtype=F64)
+            return ModalResult(theta[:k].clone(), X[:, :k].clone(), it, status, rel, restarts, h if history else None)
+
+        nan = torch.full((k,), float("nan"), dtype=F64)
+        # Rayleigh-Ritz on the start block alone
+        product(X, KX, MX)
+        gram(1)
+        rr = rayleigh_ritz(*grams(out.cpu(), 1, 1), m)
+        if rr is None or bad(rr[0], float(rr[0].abs().max())):
+            return result(torch.zeros(m, dtype=F64), C.PCG_BREAKDOWN, 0, nan, 0, [])
+        theta, Cm = rr
+        theta_ref = float(theta.max())
+        rotate(1, theta, Cm)
+        has_p, restarts, hist, status, it = False, 0, [], C.PCG_MAXITER, 0
+        rel = nan
+        for it in range(int(max_iter) + 1):
+            C.check(lib.fem_modal_residual(n, m, C.ptr(KX), C.ptr(MX), C.ptr(w), C.ptr(coef[192:]), C.ptr(W),
+                                           C.ptr(work), C.ptr(out), st), "fem_modal_residual")
+            a = 3 if has_p else 2
+            if it < max_iter:      # the one pass over the matrices, and the Gram matrices: read with the norms
+                product(W, KW, MW)
+                gram(a)
+            host = out.cpu()       # the iteration's one device-to-host read
+            rn = host[C.MODAL_OUT_NORMS: C.MODAL_OUT_NORMS + m]
+            mn = host[C.MODAL_OUT_NORMS + m: C.MODAL_OUT_NORMS + 2 * m]
+            rel = (rn / (theta * mn))[:k].clone()
+            hist.append(rel)
+            if not bool(torch.isfinite(rel).all()):
+                status = C.PCG_BREAKDOWN
+                break
+            if bool((rel <= tol).all()):
+                status = C.PCG_CONVERGED
+                break
+            if it == max_iter:
+                break
+            rr = rayleigh_ritz(*grams(host, a, a), m)
+            if rr is None and a == 3:       # restart: this iteration without P
+                restarts += 1
+                a = 2
+                rr = rayleigh_ritz(*grams(host, 3, 2), m)
+            if rr is None or bad(rr[0], theta_ref):
+                status = C.PCG_BREAKDOWN
+                break
+            theta, Cm = rr
+            rotate(a, theta, Cm)
+            has_p = True
+        return result(theta, status, it, rel, restarts, hist)
 
 
 @_scoped

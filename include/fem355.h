@@ -774,6 +774,45 @@ int fem_mpcg_solve(fem_mpcg* s, int max_iter, int chunk, int* iters, int* status
 int fem_mpcg_scalars(fem_mpcg* s, double* out);
 void fem_mpcg_destroy(fem_mpcg* s);
 
+/* ------------------------------------------------------------------ modal analysis (csrc/modal.hip)
+ * The tall-skinny kernels of the block LOBPCG that SellMatrix.eig_lowest drives for the lowest eigenpairs of
+ * K u = lambda M u. Multi-vectors are [n, nv] row-major as above (nv 2, 4 or 8; 16-byte aligned). Plain launches;
+ * every reduction is finished in workgroup order by a following one-workgroup launch (bit-reproducible); rows >= n
+ * are never read nor stored. */
+enum fem_mass_form {
+    FEM_MASS_SELL = 0,  /* mass: the plain bs = 1 SELL values of a matrix on the same pattern; M = M_s (x) I_bs */
+    FEM_MASS_DIAG = 1   /* mass: a vector d [n]; M = diag(d) (the reference's lumped mass, `solver/solver.py:1126-1134`) */
+};
+/* Y = K X and Z = M X in one sweep of the pattern: every gathered block column of X is loaded once for both (the
+ * reference forms K X column by column and M X by a broadcast, `solver/solver.py:1084-1313` at `:1207-1220`).
+ * Column j of Y equals fem_spmm's bit for bit; FEM_MASS_SELL: column j of Z equals fem_spmm on the mass matrix, per
+ * component for bs = 3. Arguments as fem_spmm. */
+int fem_spmm_km(int64_t nrows, int bs, int nv, const int64_t* slice_ptr, const int32_t* cols, const int16_t* dcols,
+                const double* vals, const double* mass, int mass_form, const double* X, double* Y, double* Z,
+                fem_stream_t stream);
+/* Output buffer of the two reductions below (doubles): G_K [am, am] row-major at 0, G_M at FEM_MODAL_OUT_GM, the norms
+ * ||R_j|| [nv] then ||MX_j|| [nv] at FEM_MODAL_OUT_NORMS. */
+#define FEM_MODAL_OUT_GM 576
+#define FEM_MODAL_OUT_NORMS 1152
+#define FEM_MODAL_OUT_LEN 1168
+/* doubles of device workspace (per-workgroup partials) that fem_modal_gram and fem_modal_residual share
+ * (`solver/solver.py:1084-1313` keeps no such state: its reductions are torch calls) */
+int64_t fem_modal_work_len(void);
+/* Gram matrices of the basis S = [X W P] (a = 3; 2: [X W]; 1: X alone): G_K = S^T (K S), G_M = S^T (M S), am = a nv,
+ * upper triangle summed in a fixed order and mirrored (`solver/solver.py:1084-1313` at `:1207-1221` builds X^T K X
+ * and X^T M X with two matmuls). vecs: [host, 9] device pointers X, W, P, KX, KW, KP, MX, MW, MP, the first a of each
+ * triple read once. */
+int fem_modal_gram(int64_t n, int nv, int a, const double* const* vecs, double* work, double* out,
+                   fem_stream_t stream);
+/* R = KX - MX diag(theta), W = w o R (w [n]: zero on fixed dofs), and the norms of R_j and MX_j over the rows with
+ * w != 0 (`solver/solver.py:1084-1313` has no residual: it runs a fixed number of sweeps). theta [device, nv]. */
+int fem_modal_residual(int64_t n, int nv, const double* KX, const double* MX, const double* w, const double* theta,
+                       double* W, double* work, double* out, fem_stream_t stream);
+/* In place, for the vectors and their K- and M-products alike (`solver/solver.py:1084-1313` at `:1304`, Y @ Z):
+ * P <- W C_W + P C_P, X <- X C_X + P with C [device, a nv, nv] row-major = [C_X; C_W; C_P]. a = 2: no old P;
+ * a = 1: X alone, P untouched. W, KW and MW are read only. vecs as fem_modal_gram. */
+int fem_modal_rotate(int64_t n, int nv, int a, double* const* vecs, const double* C, fem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
