@@ -192,6 +192,12 @@ SIGNATURES = {
     "fem_modal_gram": (_I, [_L, _I, _I, ctypes.POINTER(_P), _P, _P, _P]),
     "fem_modal_residual": (_I, [_L, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fem_modal_rotate": (_I, [_L, _I, _I, ctypes.POINTER(_P), _P, _P]),
+    "fem_pcg_set_tol": (_I, [_P, _D]),
+    "fem_sell_axpby_mass": (_I, [_L, _I, _I, _L, _P, _P, _P, _P, _P, _I, _D, _D, _P, _P]),
+    "fem_newmark_rhs": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _I, _D, _P, _P, _P, _P]),
+    "fem_newmark_update": (_I, [_L, ctypes.POINTER(_D), _I, _P, _P, _P, _P, _P, _P, _P]),
+    "fem_transient_work_len": (_L, []),
+    "fem_quadform_km": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

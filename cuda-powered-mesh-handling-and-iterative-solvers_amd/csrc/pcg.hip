@@ -3170,6 +3170,15 @@ int fem_pcg_set_entries(fem_pcg* s, int64_t entries) {
     return FEM_OK;
 }
 
+int fem_pcg_set_tol(fem_pcg* s, double tol) {
+    if (!s || !(tol >= 0.0)) {
+        set_error("fem_pcg_set_tol: needs a context and a tolerance >= 0");
+        return FEM_EARG;
+    }
+    s->tol = tol;   // copied into the device state by the next fem_pcg_start
+    return FEM_OK;
+}
+
 int fem_pcg_set_schedule(fem_pcg* s, int sched) {
     if (s->graph) {
         set_error("fem_pcg_set_schedule: drop the captured graph first (fem_pcg_use_graph(s, 0))");

@@ -540,5 +540,120 @@ def modal_solver(K, M, elements, fixed, num_nodes, num_modes=6, tol=1e-8, max_it
     ret = (freq.to(device=out, dtype=dtype), res.lam.to(device=out, dtype=dtype), modes.to(device=out, dtype=dtype))
     return ret + (res,) if return_info else ret
 
+
+# ============================================================================ transient dynamics
+# The reference stops at modes; the response in time M a + C v + K u = f(t) is integrated here by the implicit Newmark
+# scheme on the assembled matrices (system.NewmarkIntegrator, csrc/transient.hip).
+def _check_transient(what, K, M, elements, F, fixed, num_nodes, dt, steps, amplitude, u0, v0, beta, gamma, damping,
+                     record, energy_every, rtol):
+    """Every ValueError of transient_solver -- before any device call. Returns (dpn, fixed ids, record ids, history)."""
+    dpn = _check_modal(what, K, M, elements, num_nodes, 1, lambda d: (1, d))
+    if int(steps) < 1:
+        raise ValueError(f"{what}: steps must be >= 1, got {steps}")
+    _sys.newmark_constants(dt, beta, gamma, damping)
+    if rtol is not None and not float(rtol) > 0.0:
+        raise ValueError(f"{what}: rtol must be > 0, got {rtol}")
+    if int(energy_every) < 0:
+        raise ValueError(f"{what}: energy_every must be >= 0, got {energy_every}")
+    shape = tuple(F.shape) if torch.is_tensor(F) else None
+    history = shape is not None and len(shape) == 3
+    if shape not in ((num_nodes, dpn), (int(steps) + 1, num_nodes, dpn)):
+        raise ValueError(f"{what}: F must be [{num_nodes}, {dpn}] or the history [{int(steps) + 1}, {num_nodes}, {dpn}]"
+                         f", got {shape}")
+    if amplitude is not None:
+        if history:
+            raise ValueError(f"{what}: a load history [steps + 1, N, dpn] takes no amplitude")
+        if torch.is_tensor(amplitude):
+            if amplitude.dim() != 1 or amplitude.numel() != int(steps) + 1:
+                raise ValueError(f"{what}: amplitude must hold steps + 1 = {int(steps) + 1} values (t_0 .. t_steps), "
+                                 f"got {tuple(amplitude.shape)}")
+        elif not callable(amplitude):
+            raise ValueError(f"{what}: amplitude must be None, a tensor [steps + 1] or a callable of t")
+    for name, x in (("u0", u0), ("v0", v0)):
+        if x is not None and (not torch.is_tensor(x) or tuple(x.shape) != (num_nodes, dpn)):
+            raise ValueError(f"{what}: {name} must be [{num_nodes}, {dpn}]")
+    ids = _fixed_ids(what, fixed, num_nodes)
+    rec = None
+    if record is not None:
+        rec = torch.as_tensor(record).to(LONG).reshape(-1)
+        if rec.numel() and (int(rec.min()) < 0 or int(rec.max()) >= num_nodes):
+            raise ValueError(f"{what}: a recorded node lies outside [0, {num_nodes})")
+    return dpn, ids, rec, history
+
+
+def transient_solver(K, M, elements, F, fixed, num_nodes, dt, steps, amplitude=None, u0=None, v0=None,
+                     beta=0.25, gamma=0.5, damping=(0.0, 0.0), lumped=False, tol=1e-8, rtol=None, max_iter=1000,
+                     record=None, energy_every=0, callback=None, predictor=False,
+                     device="cuda:0", dtype=torch.float64, return_info=False):
+    """Response in time of M a + C v + K u = f(t), C = alpha M + beta_R K with damping = (alpha, beta_R), over `steps`
+    steps of `dt` by implicit Newmark-beta (default: average acceleration) with the nodes `fixed` held at zero.
+    K and M as in modal_solver (M the scalar factor or the full element mass; dpn 1 or 3; both assembled on the cached
+    graph); lumped=True uses the reference's lumped diagonal (the element matrices' diagonals summed per dof, clamped
+    at 1e-12, `solver/solver.py:1126-1134`). F is [N, dpn] scaled by `amplitude` (None: constant, i.e. suddenly
+    applied; a tensor [steps + 1] of the values at t_0 .. t_steps; or a callable of t), or the history [steps + 1, N,
+    dpn]. Every step solves K_eff u = b by Jacobi-PCG on one solver context, warm-started from u_n (predictor: from
+    u_n + dt v_n), to `tol` absolute on sqrt(r.z) or, with `rtol`, to rtol sqrt(b.(w o b)) of the step.
+    record: node ids whose u, v, a come back as [steps + 1, len(record), dpn]; callback(step, t, u, v, a) gets views of
+    the device state ([N dpn]); the full field history is the caller's choice. A step that does not converge stops
+    the run with one printed line; the state of the last converged step is returned.
+    Returns (u, v, a) [N, dpn] at the last step in `dtype`; with return_info also a system.TransientResult whose
+    recorded rows are shaped [steps done + 1, len(record), dpn]."""
+    what = "transient_solver"
+    dpn, ids, rec, history = _check_transient(what, K, M, elements, F, fixed, num_nodes, dt, steps, amplitude, u0, v0,
+                                              beta, gamma, damping, record, energy_every, rtol)
+    steps = int(steps)
+    dev = _dev(device)
+    el = elements.to(device=dev, dtype=LONG).contiguous()
+    npe = el.shape[1]
+    Ke = K.to(device=dev, dtype=F64).contiguous()
+    Mf = M.to(device=dev, dtype=F64)
+    g = cached_graph(el, num_nodes)
+    A = _sys.SellMatrix(g, dpn)
+    if lumped:
+        md = Mf.diagonal(dim1=1, dim2=2)                      # [Me, npe] or [Me, dpn npe]
+        if Mf.shape[1] == npe and dpn > 1:
+            md = md.repeat_interleave(dpn, dim=1)
+        dofs = (el.unsqueeze(-1) * dpn + torch.arange(dpn, device=dev).view(1, 1, dpn)).reshape(-1)
+        mass = torch.zeros(dpn * num_nodes, dtype=F64, device=dev)
+        mass.index_add_(0, dofs, md.reshape(-1))
+        mass.clamp_(min=1e-12)
+        A.add_element_matrices(Ke, el)
+    else:
+        Ms = (Mf if Mf.shape[1] == npe else Mf[:, ::dpn, ::dpn]).contiguous()
+        mass = _sys.SellMatrix(g, 1)
+        if dpn == 3:
+            A.add_stiffness_and_mass(Ke, Ms, el, mass)
+        else:
+            A.add_element_matrices(Ke, el)
+            mass.add_element_matrices(Ms, el)
+    mask = torch.zeros((num_nodes, dpn), dtype=torch.uint8, device=dev)
+    mask[ids.to(dev)] = 1
+    integ = _sys.NewmarkIntegrator(A, mass, mask.view(-1), dt, beta, gamma, damping, tol=tol, rtol=rtol,
+                                   max_iter=max_iter, predictor=predictor)
+    try:
+        Fd = F.to(device=dev, dtype=F64).reshape(-1, num_nodes * dpn).contiguous()
+        if history:
+            amps = [1.0] * (steps + 1)
+        elif amplitude is None:
+            amps = [1.0] * (steps + 1)
+        elif torch.is_tensor(amplitude):
+            amps = [float(x) for x in amplitude.to(dtype=F64).cpu()]
+        else:
+            amps = [float(amplitude(k * float(dt))) for k in range(steps + 1)]
+        vec = lambda x: None if x is None else x.reshape(-1)
+        integ.start(vec(u0), vec(v0), amps[0] * Fd[0])
+        load = (lambda k: (Fd[k], 1.0)) if history else (lambda k: (Fd[0], amps[k]))
+        rdofs = None
+        if rec is not None:
+            rdofs = (rec.to(dev).unsqueeze(-1) * dpn + torch.arange(dpn, device=dev)).reshape(-1)
+        res = integ.run(steps, load, record=rdofs, energy_every=int(energy_every), callback=callback)
+        if rec is not None:
+            res.rec_u, res.rec_v, res.rec_a = (r.reshape(r.shape[0], -1, dpn) for r in (res.rec_u, res.rec_v, res.rec_a))
+        out = torch.device(device)
+        ret = tuple(x.view(num_nodes, dpn).to(device=out, dtype=dtype).clone() for x in (integ.u, integ.v, integ.a))
+    finally:
+        integ.close()
+    return ret + (res,) if return_info else ret
+
 # every public function runs in the scope of the device its `device` argument names (_capi.on_device)
 C.scope_module(globals())

@@ -1023,6 +1023,56 @@ class SellMatrix:
             has_p = True
         return result(theta, status, it, rel, restarts, hist)
 
+    # ---------------------------------------------------------------- combinations with the mass (csrc/transient.hip)
+    def _held_values(self):
+        """(values, layout_a) as the transient kernels read this matrix: the bs = 3 layout A when it holds the values,
+        else the plain planes (a bs = 1 matrix in the solver layout goes through plain_values())."""
+        if self._sl_ok and self.bs == 3:
+            return self._svals, 1
+        return self.plain_values(), 0
+
+    def scaled_add_mass(self, mass, cK, cM):
+        """A new SellMatrix cK K + cM M on the same graph (include/fem355.h fem_sell_axpby_mass), `mass` as in
+        matvec_km_multi: the effective matrix of an implicit time step, or a shifted K - sigma M. It is held in the
+        solver layout exactly when this matrix is bs = 3 in the solver layout -- the PCG then reads it as it is --
+        and in the plain planes otherwise. matvec, jacobi, pcg and csr work on the result unchanged."""
+        form, mass = self._mass_form("scaled_add_mass", mass)
+        mv = self._mass_values(form, mass)
+        src, la = self._held_values()
+        out = SellMatrix(self.g, self.bs)
+        out.use16 = self.use16
+        dst = out._svals_buf() if la else out._plain_buf()
+        C.check(C.lib().fem_sell_axpby_mass(self.g.n_nodes, self.bs, la, self.g.sell_entries, C.ptr(self.g.slice_ptr),
+                                            C.ptr(self.g.rowptr), C.ptr(self.g.diagpos), C.ptr(src), C.ptr(mv), form,
+                                            float(cK), float(cM), C.ptr(dst), C.stream(self.device)),
+                "fem_sell_axpby_mass")
+        out._fresh = False
+        out._sl_ok, out._plain_ok = bool(la), not la
+        return out
+
+    def quadforms(self, mass, x, y):
+        """Device tensor [2] = (x^T K x, y^T M y) in one sweep of the pattern (include/fem355.h fem_quadform_km);
+        bit-reproducible. `mass` as in matvec_km_multi."""
+        form, mass = self._mass_form("quadforms", mass)
+        if x.numel() != self.n or y.numel() != self.n:
+            raise ValueError(f"quadforms: x and y must hold {self.n} values, got {x.numel()} and {y.numel()}")
+        lib = C.lib()
+        X = torch.stack((x.to(device=self.device, dtype=F64).reshape(-1),
+                         y.to(device=self.device, dtype=F64).reshape(-1)), dim=1).contiguous()
+        mv = self._mass_values(form, mass)
+        kv, la = self._held_values()
+        work = torch.empty(int(lib.fem_transient_work_len()), dtype=F64, device=self.device)
+        out = torch.empty(2, dtype=F64, device=self.device)
+        cols, dcols = self._multi_cols()
+        C.check(lib.fem_quadform_km(self.g.n_nodes, self.bs, la, C.ptr(self.g.slice_ptr), cols, dcols, C.ptr(kv),
+                                    C.ptr(mv), form, C.ptr(X), C.ptr(work), C.ptr(out), C.stream(self.device)),
+                "fem_quadform_km")
+        return out
+
+    def energy(self, mass, u, v):
+        """E = u^T K u / 2 + v^T M v / 2 (one device-to-host read)."""
+        return 0.5 * float(self.quadforms(mass, u, v).sum())
+
 
 @_scoped
 class MatFreeOperator:
@@ -1272,6 +1322,263 @@ class PcgRunner:
 
     def close(self):
         if self.h:
+            self.lib.fem_pcg_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ============================================================================ transient dynamics (csrc/transient.hip)
+def newmark_constants(dt, beta=0.25, gamma=0.5, damping=(0.0, 0.0)):
+    """The constants of a Newmark-beta step of M a + C v + K u = f with C = alpha M + beta_R K, damping = (alpha,
+    beta_R): a0..a5, the factors of K_eff = cK K + cM M, and `coef`, the 12 values fem_newmark_update takes
+    (include/fem355.h). ValueError unless dt > 0, beta > 0, gamma >= 1/2 and both damping factors are >= 0 -- no device
+    call. A conditionally stable pair (2 beta < gamma) is accepted: dt is then the caller's business."""
+    dt, beta, gamma = float(dt), float(beta), float(gamma)
+    if not dt > 0.0:
+        raise ValueError(f"Newmark: dt must be > 0, got {dt}")
+    if not beta > 0.0 or not gamma >= 0.5:
+        raise ValueError(f"Newmark: needs beta > 0 and gamma >= 1/2 (the explicit beta = 0 scheme is out of scope), "
+                         f"got beta = {beta}, gamma = {gamma}")
+    try:
+        alpha, beta_r = (float(d) for d in damping)
+    except (TypeError, ValueError):
+        raise ValueError(f"Newmark: damping must be the pair (alpha, beta_R), got {damping!r}") from None
+    if not alpha >= 0.0 or not beta_r >= 0.0:
+        raise ValueError(f"Newmark: the Rayleigh factors must be >= 0, got alpha = {alpha}, beta_R = {beta_r}")
+    a0, a1, a2 = 1.0 / (beta * dt * dt), gamma / (beta * dt), 1.0 / (beta * dt)
+    a3, a4, a5 = 1.0 / (2.0 * beta) - 1.0, gamma / beta - 1.0, 0.5 * dt * (gamma / beta - 2.0)
+    c = dict(dt=dt, beta=beta, gamma=gamma, alpha=alpha, beta_r=beta_r, a0=a0, a1=a1, a2=a2, a3=a3, a4=a4, a5=a5,
+             cK=1.0 + a1 * beta_r, cM=a0 + a1 * alpha)
+    c["coef"] = [a0, a2, a3, dt * (1.0 - gamma), dt * gamma,
+                 a0 + alpha * a1, a2 + alpha * a4, a3 + alpha * a5,
+                 beta_r * a1, beta_r * a4, beta_r * a5, dt]
+    return c
+
+
+@dataclass
+class TransientResult:
+    """NewmarkIntegrator.run: what happened step by step. Entry 0 of the recorded rows and of `times` is the start."""
+    times: torch.Tensor            # [steps done + 1] (host)
+    iterations: list               # PCG iterations of every step tried (the stopped one included)
+    status: list                   # _capi.PCG_* of every step tried
+    steps_done: int                # steps whose solve converged
+    rec_u: torch.Tensor = None     # [steps done + 1, len(record)] (device): the recorded dofs
+    rec_v: torch.Tensor = None
+    rec_a: torch.Tensor = None
+    energy_steps: list = None      # the steps whose energy was taken (0, energy_every, ...)
+    energies: torch.Tensor = None  # [len(energy_steps)] (host): u^T K u / 2 + v^T M v / 2
+
+    @property
+    def converged(self):
+        return all(s == C.PCG_CONVERGED for s in self.status)
+
+
+@_scoped
+class NewmarkIntegrator:
+    """Implicit Newmark-beta integration of M a + C v + K u = f(t), C = alpha M + beta_R K, on an assembled K (`A`) and
+    a mass as in SellMatrix.matvec_km_multi (M_s (x) I_bs on the same Graph, or a lumped diagonal).
+    Set-up forms K_eff = cK K + cM M once, in the layout the solver reads (scaled_add_mass), its Jacobi weights with
+    zeros on the dofs of `fixed_mask` (uint8 [n]; u, v, a stay zero there, no row is eliminated), and ONE PCG context
+    over fixed b and x buffers. A step is one pattern sweep for the right-hand side (fem_newmark_rhs), one
+    fem_pcg_solve on that context warm-started from u_n (`predictor`: from u_n + dt v_n) and one fused vector kernel
+    (fem_newmark_update). With K_eff in layout A the context converts nothing per step; with plain values (bs = 1,
+    FEM355_SL=0, int32 columns) its paired copy is rebuilt at every start.
+    `tol` is absolute on sqrt(r.z); `rtol`, when given, sets every step's tolerance to rtol sqrt(b.(w o b)) of that
+    step's right-hand side (one extra device-to-host read per step). A step whose solve does not end converged leaves
+    the state at the step before."""
+
+    def __init__(self, A: SellMatrix, mass, fixed_mask, dt, beta=0.25, gamma=0.5, damping=(0.0, 0.0), tol=1e-8,
+                 rtol=None, max_iter=1000, schedule=None, predictor=False, chunk=32):
+        self.c = newmark_constants(dt, beta, gamma, damping)
+        self.form, mass = A._mass_form("NewmarkIntegrator", mass)
+        if rtol is not None and not float(rtol) > 0.0:
+            raise ValueError(f"NewmarkIntegrator: rtol must be > 0, got {rtol}")
+        self.lib = C.lib()
+        self.A, self.mass, self.device = A, mass, A.device
+        self.tol, self.rtol, self.max_iter, self.chunk = float(tol), rtol, int(max_iter), int(chunk)
+        self.predictor = bool(predictor)
+        self.events = None               # a list: step() appends its four torch events (rhs | solve | update)
+        dev, n = A.device, A.n
+        self._mv = A._mass_values(self.form, mass)
+        self._kv, self._la = A._held_values()
+        self.Keff = A.scaled_add_mass(mass, self.c["cK"], self.c["cM"])
+        fixed_mask = fixed_mask.to(device=dev, dtype=torch.uint8).contiguous().view(-1)
+        if fixed_mask.numel() != n:
+            raise ValueError(f"NewmarkIntegrator: fixed_mask must hold {n} values, got {fixed_mask.numel()}")
+        self.fixed_mask = fixed_mask
+        self.w = self.Keff.jacobi(fixed_mask)
+        self.free = self.w != 0
+        z = lambda *s: torch.zeros(s, dtype=F64, device=dev)
+        self.b, self.x, self.u, self.v, self.a, self.Y = z(n), z(n), z(n), z(n), z(n), z(n, 2)
+        self._coef = (ctypes.c_double * 12)(*self.c["coef"])
+        self.t, self.step_no = 0.0, 0
+        self.h = ctypes.c_void_p()
+        K = self.Keff
+        self.schedule = _schedule(False, schedule, K.bs)
+        plain = self.schedule == SCHED_FUSED
+        self._stream = C.stream(dev)
+        C.check(self.lib.fem_pcg_create(K.g.n_nodes, K.bs, C.ptr(K.g.slice_ptr), C.ptr(K.g.cols),
+                                        K.solver_vals_ptr(plain), C.ptr(self.b), C.ptr(self.x), C.ptr(self.w),
+                                        C.MODE_PCG, self.tol, 1e-30, None, 0, self._stream, ctypes.byref(self.h)),
+                "fem_pcg_create")
+        C.check(self.lib.fem_pcg_set_schedule(self.h, self.schedule), "fem_pcg_set_schedule")
+        C.check(self.lib.fem_pcg_set_entries(self.h, K.g.sell_entries), "fem_pcg_set_entries")
+        K.attach_cols16(self.h)
+        K.attach_layout(self.h, plain)
+
+    # -------------------------------------------------------------- start
+    def _vec(self, x, what):
+        if x is None:
+            return torch.zeros(self.A.n, dtype=F64, device=self.device)
+        x = x.to(device=self.device, dtype=F64).reshape(-1)
+        if x.numel() != self.A.n:
+            raise ValueError(f"NewmarkIntegrator: {what} must hold {self.A.n} values, got {x.numel()}")
+        return x
+
+    def _mass_times(self, x):
+        if self.form == C.MASS_DIAG:
+            return self._mv * x
+        bs, N = self.A.bs, self.A.g.n_nodes
+        return self.mass.matvec_multi(x.view(N, bs).contiguous()).reshape(-1)
+
+    def start(self, u0=None, v0=None, f0=None):
+        """Set the state at t = 0: u0, v0 (zeroed on the fixed dofs) and a_0 = M^-1 (f0 - C v0 - K u0) on the free
+        dofs -- a division for the diagonal mass, Mg.pcg_multi over the bs components (rtol 1e-12 of each column's own
+        sqrt(r0.z0)) for the SELL mass, whose fixed dofs must then be whole nodes."""
+        A, c, free = self.A, self.c, self.free
+        u0, v0, f0 = self._vec(u0, "u0") * free, self._vec(v0, "v0") * free, self._vec(f0, "f0")
+        r = f0 - A.matvec(u0 + c["beta_r"] * v0)
+        if c["alpha"] != 0.0:
+            r = r - c["alpha"] * self._mass_times(v0)
+        r = r * free
+        if self.form == C.MASS_DIAG:
+            a0 = torch.where(free, r / self._mv, torch.zeros_like(r))
+        else:
+            bs, N = A.bs, A.g.n_nodes
+            fm = self.fixed_mask.view(N, bs)
+            if bs > 1 and bool((fm != fm[:, :1]).any()):
+                raise ValueError("NewmarkIntegrator: with the SELL mass a node is fixed in all its components or none")
+            wm = self.mass.jacobi(fm[:, 0].contiguous())
+            R = r.view(N, bs).contiguous()
+            nrm = torch.sqrt((R * (wm[:, None] * R)).sum(0)).cpu()
+            a0 = torch.zeros_like(R)
+            nz = [j for j in range(bs) if float(nrm[j]) > 0.0]   # a zero column has a_0 = 0 (and no search direction)
+            if nz:
+                res = self.mass.pcg_multi(R[:, nz].contiguous(), None, w=wm, mode=C.MODE_PCG,
+                                          tol=[1e-12 * float(nrm[j]) for j in nz], max_iter=10000)
+                if any(s != C.PCG_CONVERGED for s in res.status):
+                    raise C.FemError(f"NewmarkIntegrator: the mass solve for a_0 stopped with status {res.status}")
+                a0[:, nz] = res.x
+            a0 = a0.reshape(-1) * free
+        self.u.copy_(u0)
+        self.v.copy_(v0)
+        self.a.copy_(a0)
+        k = c["coef"]
+        self.Y[:, 1] = k[5] * self.u + k[6] * self.v + k[7] * self.a
+        self.Y[:, 0] = k[8] * self.u + k[9] * self.v + k[10] * self.a
+        self.x.copy_(self.u + c["dt"] * self.v if self.predictor else self.u)
+        self.t, self.step_no = 0.0, 0
+        return self
+
+    # -------------------------------------------------------------- one step
+    def rhs(self, F=None, amp=1.0):
+        """b <- amp F + M yM + K yK (the K stream is read only with stiffness damping)."""
+        A = self.A
+        if F is not None and (not F.is_cuda or F.dtype != F64 or F.numel() != A.n or not F.is_contiguous()):
+            raise ValueError(f"NewmarkIntegrator: F must be a contiguous fp64 device tensor of {A.n} values")
+        cols, dcols = A._multi_cols()
+        kv = C.ptr(self._kv) if self.c["beta_r"] != 0.0 else None
+        C.check(self.lib.fem_newmark_rhs(A.g.n_nodes, A.bs, self._la, C.ptr(A.g.slice_ptr), cols, dcols, kv,
+                                         C.ptr(self._mv), self.form, float(amp), C.ptr(F), C.ptr(self.Y),
+                                         C.ptr(self.b), self._stream), "fem_newmark_rhs")
+
+    def update(self):
+        C.check(self.lib.fem_newmark_update(self.A.n, self._coef, 1 if self.predictor else 0, C.ptr(self.x),
+                                            C.ptr(self.u), C.ptr(self.v), C.ptr(self.a), C.ptr(self.w), C.ptr(self.Y),
+                                            self._stream), "fem_newmark_update")
+
+    def step(self, F=None, amp=1.0):
+        """Advance to t + dt under the load amp F at the NEW time -> (PCG iterations, status). A solve that does not end
+        converged leaves u, v, a and t at the step before."""
+        ev = None
+        if self.events is not None:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record()
+        self.rhs(F, amp)
+        if ev:
+            ev[1].record()
+        zero = False
+        if self.rtol is not None:
+            bn = float(torch.sqrt(torch.dot(self.b, self.w * self.b)))
+            zero = bn == 0.0   # nothing moves and nothing pushes: u_new = 0
+            if not zero:
+                C.check(self.lib.fem_pcg_set_tol(self.h, float(self.rtol) * bn), "fem_pcg_set_tol")
+        it, stt, rz = ctypes.c_int(0), ctypes.c_int(C.PCG_CONVERGED), ctypes.c_double()
+        if zero:
+            self.x.zero_()
+        else:
+            C.check(self.lib.fem_pcg_solve(self.h, self.max_iter, self.chunk, ctypes.byref(it), ctypes.byref(stt),
+                                           ctypes.byref(rz)), "fem_pcg_solve")
+            _check_sync(stt.value)
+        if ev:
+            ev[2].record()
+        if stt.value != C.PCG_CONVERGED:
+            self.x.copy_(self.u + self.c["dt"] * self.v if self.predictor else self.u)
+            return it.value, stt.value
+        self.update()
+        if ev:
+            ev[3].record()
+            self.events.append(ev)
+        self.step_no += 1
+        self.t = self.step_no * self.c["dt"]
+        return it.value, stt.value
+
+    # -------------------------------------------------------------- a whole run
+    def run(self, steps, load=None, record=None, energy_every=0, callback=None):
+        """`steps` steps from the started state. load(k) -> (F or None, amp) gives the load at step k = 1..steps (F a
+        contiguous fp64 device tensor [n]). record: dof indices (device int64) whose u, v, a are kept per step.
+        energy_every = m > 0: the energy at steps 0, m, 2m, ... (read back once, at the end). callback(step, t, u, v,
+        a) gets the device state itself (views, not copies). A step that does not converge stops the run and prints
+        `Transient solver: step k stopped with status S after N iterations`. Returns a TransientResult."""
+        its, stts, recs, en, en_steps = [], [], [], [], []
+
+        def keep(k):
+            if record is not None:
+                recs.append(torch.stack((self.u[record], self.v[record], self.a[record])))
+            if energy_every and k % energy_every == 0:
+                en.append(self.A.quadforms(self.mass, self.u, self.v))
+                en_steps.append(k)
+
+        keep(0)
+        done = 0
+        for k in range(1, int(steps) + 1):
+            F, amp = load(k) if load is not None else (None, 0.0)
+            it, stt = self.step(F, amp)
+            its.append(it)
+            stts.append(stt)
+            if stt != C.PCG_CONVERGED:
+                print(f"Transient solver: step {k} stopped with status {stt} after {it} iterations")
+                break
+            done = k
+            keep(k)
+            if callback is not None:
+                callback(k, self.t, self.u, self.v, self.a)
+        res = TransientResult(torch.arange(done + 1, dtype=F64) * self.c["dt"], its, stts, done)
+        if record is not None:
+            R = torch.stack(recs)   # [steps + 1, 3, len]
+            res.rec_u, res.rec_v, res.rec_a = R[:, 0], R[:, 1], R[:, 2]
+        if energy_every:
+            res.energy_steps = en_steps
+            res.energies = 0.5 * torch.stack(en).sum(1).cpu()
+        return res
+
+    def close(self):
+        if getattr(self, "h", None):
             self.lib.fem_pcg_destroy(self.h)
             self.h = ctypes.c_void_p()
 

@@ -445,6 +445,10 @@ int fem_pcg_set_schedule(fem_pcg* s, int sched);
  * pattern build; the paired copy is sized from it): spares fem_pcg_start the device-to-host read (a host sync)
  * before it builds that copy. Optional; without it fem_pcg_start reads the count itself. */
 int fem_pcg_set_entries(fem_pcg* s, int64_t entries);
+/* [host] the stop tolerance of fem_pcg_create, replaced: a host-side field that takes effect at the next fem_pcg_start
+ * (so at the next fem_pcg_solve). The time integrator keeps one context for a whole run and sets each step's tolerance
+ * from that step's right-hand side (the reference creates its solver state per call, `solver/solver.py:766-812`). */
+int fem_pcg_set_tol(fem_pcg* s, double tol);
 /* the schedule the context runs (valid after fem_pcg_start: 3 may have fallen back to 2) */
 int fem_pcg_get_schedule(fem_pcg* s);
 /* [sync] over the slices [s_begin, s_end) of the context's matrix (s_end < 0: to the last): the slices stored with
@@ -812,6 +816,44 @@ int fem_modal_residual(int64_t n, int nv, const double* KX, const double* MX, co
  * P <- W C_W + P C_P, X <- X C_X + P with C [device, a nv, nv] row-major = [C_X; C_W; C_P]. a = 2: no old P;
  * a = 1: X alone, P untouched. W, KW and MW are read only. vecs as fem_modal_gram. */
 int fem_modal_rotate(int64_t n, int nv, int a, double* const* vecs, const double* C, fem_stream_t stream);
+
+/* ------------------------------------------------------------------ transient dynamics (csrc/transient.hip)
+ * The kernels of the implicit Newmark integrator that system.py NewmarkIntegrator drives for
+ * M a + C v + K u = f(t), C = alpha M + beta_R K (the reference has no time integration; its only routine on K and M
+ * together is `vectorized_modal_solver`, `solver/solver.py:1084-1313`). Same rules as the modal kernels: plain
+ * launches, reductions finished in workgroup order by a one-workgroup launch (bit-reproducible), rows >= n never read
+ * nor stored. kvals is read in the layout it is held in: layout_a = 0 the plain SELL planes (bs 1 or 3), layout_a = 1
+ * the bs = 3 solver layout A (16-bit deltas required). mass / mass_form as fem_spmm_km. */
+/* out = cK K + cM M in K's own layout (out may not alias kvals), entries = slice_ptr[nslices]. FEM_MASS_SELL: every
+ * block gets cM ms on its bs diagonal components; FEM_MASS_DIAG: only the diagonal entry of each row's own block
+ * (slot diagpos - rowptr of the row) gets cM d. Padding entries stay 0. (`solver/solver.py:1084-1313` never forms a
+ * combination of K and M.) */
+int fem_sell_axpby_mass(int64_t nrows, int bs, int layout_a, int64_t entries, const int64_t* slice_ptr,
+                        const int32_t* rowptr, const int32_t* diagpos, const double* kvals, const double* mass,
+                        int mass_form, double cK, double cM, double* out, fem_stream_t stream);
+/* b = amp F + M Y[:, 1] + K Y[:, 0] for Y [n, 2] row-major (16-byte aligned) in one sweep of the pattern, one
+ * accumulator per row (entries in slot order, the K term of an entry before its mass term). kvals NULL: no stiffness
+ * damping, the K stream is not read. F NULL: no load. (The reference applies K by `compute_nodal_forces`,
+ * `solver/element.py:429-464`, one vector at a time.) */
+int fem_newmark_rhs(int64_t nrows, int bs, int layout_a, const int64_t* slice_ptr, const int32_t* cols,
+                    const int16_t* dcols, const double* kvals, const double* mass, int mass_form, double amp,
+                    const double* F, const double* Y, double* b, fem_stream_t stream);
+/* One pass over the vectors after a step's solve, x = u_new on entry. coef [host, 12] = {a0, a2, a3, dt (1 - gamma),
+ * dt gamma, mu, mv, ma, ku, kv, ka, dt}:
+ *   a <- a0 (x - u) - a2 v - a3 a;  v <- v + coef[3] a_old + coef[4] a;  u <- x;
+ *   Y[:, 1] <- mu u + mv v + ma a;  Y[:, 0] <- ku u + kv v + ka a;  predictor != 0: x <- u + dt v
+ * Dofs with w = 0 (fixed) are stored as zeros in all six. All vectors [n], Y [n, 2], 16-byte aligned. (No counterpart in
+ * the reference, `solver/solver.py`.) */
+int fem_newmark_update(int64_t n, const double* coef, int predictor, double* x, double* u, double* v, double* a,
+                       const double* w, double* Y, fem_stream_t stream);
+/* doubles of device workspace (per-workgroup partials) of fem_quadform_km (`solver/solver.py` keeps no such state) */
+int64_t fem_transient_work_len(void);
+/* out [device, 2] = (x^T K x, y^T M y) for X = [x | y] [n, 2] row-major in one sweep: the energy
+ * E = (out[0] + out[1]) / 2 with X = [u | v] (`solver/solver.py:1084-1313` at `:1207-1221` forms such products with
+ * two matmuls). */
+int fem_quadform_km(int64_t nrows, int bs, int layout_a, const int64_t* slice_ptr, const int32_t* cols,
+                    const int16_t* dcols, const double* kvals, const double* mass, int mass_form, const double* X,
+                    double* work, double* out, fem_stream_t stream);
 
 #ifdef __cplusplus
 }
