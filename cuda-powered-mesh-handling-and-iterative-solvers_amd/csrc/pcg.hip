@@ -1921,6 +1921,13 @@ struct fem_pcg {
     unsigned* pk_sync;    // (18 + G) lines, zeroed before every launch
     int pk_ovf;           // overflow build (more than PK_MAXS slices per wave)
     double* pk_v;         // [n] v of the overflow rows
+    // diagonal-free value stream (FEM_TUNE_PK_OFFDIAG, sell_pair.hpp k_sell_offdiag): private to this context, always
+    // owned by it (also over a caller's solver-layout arrays), rebuilt from pvals by every fem_pcg_start
+    int pk_od;            // the persistent launches of this solve read it (OD build)
+    double* pk_ovals;     // [entries] values, diagonal-free slices at width w - 1
+    int16_t* pk_oucol;    // delta lists (pucol's size), diagonal-free slices without their 0
+    int32_t* pk_kd;       // [nslices] list index of the diagonal, -1: the slice kept its full rows
+    double* pk_diag;      // [n] diagonal of the rows of diagonal-free slices (0 elsewhere)
     int pk_coop;          // launch through hipLaunchCooperativeKernel (fem_pcg_solve; FEM_TUNE_PK_COOP elsewhere)
     int pk_gv;            // pipelined persistent iteration (FEM_TUNE_PK_GV, pcg_persist_gv.hpp)
     double* gv_buf;       // its vectors: u, w, q, z, m[0], m[1] ([6 n])
@@ -3079,7 +3086,8 @@ int fem_pcg_create(int64_t nrows, int bs, const int64_t* slice_ptr, const int32_
         return FEM_EARG;
     }
     fem_pcg* s = new fem_pcg();
-    s->tune = FEM_TUNE_REVERSE | FEM_TUNE_PAIR | FEM_TUNE_PK_SC1 | FEM_TUNE_PK_PACK | FEM_TUNE_PK_UNI | FEM_TUNE_UPD1;
+    s->tune = FEM_TUNE_REVERSE | FEM_TUNE_PAIR | FEM_TUNE_PK_SC1 | FEM_TUNE_PK_PACK | FEM_TUNE_PK_UNI | FEM_TUNE_UPD1 |
+              FEM_TUNE_PK_OFFDIAG;
     s->nrows = nrows;
     s->bs = bs;
     s->nslices = cdiv(nrows, 64);
@@ -3380,7 +3388,20 @@ static int dist_maxs(const fem_pcg* s) {
 
 // small: slices per wave of the packed assignment (1, 2, 3-4 select the one-, two-, four-slot build with 8, 4, 4 lane
 // pairs in flight; 0 the 7-slot build with 2)
-static const void* persist_fn(bool prof, bool gsc1, bool ovf = false, int small = 0) {
+// od: the build that streams the diagonal-free values (FEM_TUNE_PK_OFFDIAG), one per build below
+static const void* persist_fn(bool prof, bool gsc1, bool ovf = false, int small = 0, bool od = false) {
+    if (od) {
+        if (small >= 1 && small <= 4 && !prof && !ovf && gsc1)
+            return small == 1 ? (const void*)k_pcg_persist<1, false, true, false, false, true>
+                 : small == 2 ? (const void*)k_pcg_persist<2, false, true, false, false, true>
+                              : (const void*)k_pcg_persist<4, false, true, false, false, true>;
+        if (ovf) return gsc1 ? (const void*)k_pcg_persist<PK_MAXS, false, true, true, false, true>
+                             : (const void*)k_pcg_persist<PK_MAXS, false, false, true, false, true>;
+        if (prof) return gsc1 ? (const void*)k_pcg_persist<PK_MAXS, true, true, false, false, true>
+                              : (const void*)k_pcg_persist<PK_MAXS, true, false, false, false, true>;
+        return gsc1 ? (const void*)k_pcg_persist<PK_MAXS, false, true, false, false, true>
+                    : (const void*)k_pcg_persist<PK_MAXS, false, false, false, false, true>;
+    }
     if (small >= 1 && small <= 4 && !prof && !ovf && gsc1)
         return small == 1 ? (const void*)k_pcg_persist<1, false, true>
              : small == 2 ? (const void*)k_pcg_persist<2, false, true>
@@ -3404,8 +3425,78 @@ static int persist_maxs(const fem_pcg* s) { return s->bs == 3 ? P3_MAXS : PK_MAX
 // projections, capacity (every wave <= MAXS slices, else the overflow build), one resident PK_T-thread workgroup per CU
 static int persist_setup_dist(fem_pcg* s);
 
+// The diagonal-free stream of this solve (FEM_TUNE_PK_OFFDIAG): schedule 3 on one GPU, bs = 1, slice-uniform lists,
+// not the pipelined build. One pass over the paired values (k_sell_offdiag) at every start, since the values may
+// have changed; the buffers are allocated once per context like pvals (the pattern of a context never changes).
+static int offdiag_build(fem_pcg* s) {
+    s->pk_od = 0;
+    if (!(s->tune & FEM_TUNE_PK_OFFDIAG) || !s->persist || s->bs != 1 || s->pd || s->pk_gv ||
+        !(s->tune & FEM_TUNE_PK_UNI) || !s->puoff || !s->pucol)
+        return FEM_OK;
+    if (!s->pk_ovals) {
+        int64_t ent = s->sell_ent;
+        if (ent < 0) {   // not given by the caller: one device-to-host read (a host sync)
+            FEM_HIP(hipMemcpyAsync(&ent, s->slice_ptr + s->nslices, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+            FEM_HIP(hipStreamSynchronize(s->stream));
+        }
+        FEM_HIP(pool_alloc((void**)&s->pk_ovals, sizeof(double) * (size_t)(ent > 0 ? ent : 1), s->stream, true));
+        FEM_HIP(pool_alloc((void**)&s->pk_oucol, sizeof(int16_t) * (size_t)(2 * (ent / 64) + 2), s->stream, true));
+        FEM_HIP(pool_alloc((void**)&s->pk_kd, sizeof(int32_t) * (size_t)s->nslices, s->stream, true));
+        FEM_HIP(pool_alloc((void**)&s->pk_diag, sizeof(double) * (size_t)s->n, s->stream, true));
+    }
+    hipLaunchKernelGGL(k_sell_offdiag, dim3((unsigned)cdiv(s->nslices, 4)), dim3(256), 0, s->stream, s->nslices,
+                       s->nrows, s->slice_ptr, s->pvals, s->puoff, s->pucol, s->pk_ovals, s->pk_oucol, s->pk_kd,
+                       s->pk_diag);
+    FEM_LAUNCHED();
+    s->pk_od = 1;
+    return FEM_OK;
+}
+
+int fem_pcg_offdiag_slices(fem_pcg* s, int64_t* od_slices, int64_t* nslices, int64_t* bytes) {
+    *od_slices = 0;
+    *nslices = s->nslices;
+    *bytes = 0;
+    if (!s->persist || !s->pk_od || s->nslices == 0) return FEM_OK;
+    std::vector<int32_t> h((size_t)s->nslices);
+    FEM_HIP(hipMemcpyAsync(h.data(), s->pk_kd, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, s->stream));
+    FEM_HIP(hipStreamSynchronize(s->stream));
+    int64_t c = 0;
+    if (s->pk_ovf) {   // overflow build: only the register slots' slices (the first PK_MAXS of every wave's `pack`)
+        const int G = s->pk_grid;
+        const int64_t maxL = (s->nslices + G - 1) / G;
+        const int64_t m = (maxL + PK_WAVES - 1) / PK_WAVES;
+        for (int L = 0; L < G; ++L) {
+            const int64_t sL0 = (int64_t)L * s->nslices / G, nL = (int64_t)(L + 1) * s->nslices / G - sL0;
+            for (int wv = 0; wv < PK_WAVES; ++wv) {
+                const int64_t lo = std::min<int64_t>(wv * m, nL);
+                const int64_t nreg = std::min<int64_t>(std::min<int64_t>(nL - lo, m), PK_MAXS);
+                for (int64_t j = 0; j < nreg; ++j) c += h[(size_t)(sL0 + lo + j)] >= 0;
+            }
+        }
+    } else {
+        for (int32_t k : h) c += k >= 0;
+    }
+    *od_slices = c;
+    *bytes = c * 64 * (int64_t)sizeof(double);   // one value per row of a diagonal-free slice
+    return FEM_OK;
+}
+
+int fem_pcg_debug_offdiag(fem_pcg* s, const int32_t* rowptr, double* vals) {
+    if (!s->persist || !s->pk_od || !s->cols16) {
+        set_error("fem_pcg_debug_offdiag: the started context reads no diagonal-free stream");
+        return FEM_EARG;
+    }
+    hipLaunchKernelGGL(k_sell_od_unpair, dim3(stream_grid(s->nslices * 64, 256)), dim3(256), 0, s->stream, s->nslices,
+                       s->slice_ptr, s->cols16, s->puoff, s->pucol, s->pk_kd, s->pk_diag, rowptr, s->nrows,
+                       s->pk_ovals, vals);
+    FEM_LAUNCHED();
+    FEM_HIP(hipStreamSynchronize(s->stream));
+    return FEM_OK;
+}
+
 static int persist_setup(fem_pcg* s) {
     s->persist = 0;
+    s->pk_od = 0;
     if (s->pd) return persist_setup_dist(s);
     if (!s->persist_req) return FEM_OK;
     if ((s->bs != 1 && s->bs != 3) || !s->paired || s->dist || s->mode == FEM_MODE_CG_CONSTRAINED || s->nslices == 0)
@@ -3429,10 +3520,12 @@ static int persist_setup(fem_pcg* s) {
         int& slot = occ_cache[s->bs == 3][dev & 63];
         if (slot == 0) {
             int res = 1;
-            for (int v = 0; v < (s->bs == 3 ? 2 : 9) && res == 1; ++v) {
+            for (int vv = 0; vv < (s->bs == 3 ? 2 : 18) && res == 1; ++vv) {
+                const int v = vv % 9;
+                const bool od = vv >= 9;   // the diagonal-free builds
                 const void* f = s->bs == 3 ? persist3_fn(v == 1, false)
-                              : v >= 6 ? persist_fn(false, true, false, v == 8 ? 4 : v - 5)
-                                       : persist_fn((v & 1) && v < 4, v & 2, v >= 4);
+                              : v >= 6 ? persist_fn(false, true, false, v == 8 ? 4 : v - 5, od)
+                                       : persist_fn((v & 1) && v < 4, v & 2, v >= 4, 0, od);
                 FEM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)persist_lds(s)));
                 int nb = 0;
                 FEM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, PK_T, persist_lds(s)));
@@ -3494,7 +3587,7 @@ static int persist_setup(fem_pcg* s) {
             s->pk_gv = slot == 1;
         }
     }
-    return FEM_OK;
+    return offdiag_build(s);
 }
 
 // schedule 3 over a row-partitioned multi-rank system (fem_pcg_set_rows / fem_pcg_set_peers already ran): the
@@ -3602,6 +3695,15 @@ static int launch_persist(fem_pcg* s, int k, unsigned long long* prof) {
     a.pub = nullptr;
     a.b = s->b;
     a.init = 0;
+    a.diag = nullptr;
+    a.vals_full = a.vals;
+    a.ucol_full = a.ucol;
+    const bool od = s->pk_od && s->bs == 1 && !s->pd && !s->pk_gv;
+    if (od) {   // the context's diagonal-free stream instead of the shared values and lists
+        a.vals = s->pk_ovals;
+        a.ucol = s->pk_oucol;
+        a.diag = s->pk_diag;
+    }
     if (s->pd) {   // distributed: this rank's slices, comm blocks, the init on the first launch after start
         const int64_t S0 = s->pd_split[s->pd_rank], S1 = s->pd_split[s->pd_rank + 1];
         a.nslices = S1 - S0;
@@ -3678,7 +3780,7 @@ static int launch_persist(fem_pcg* s, int k, unsigned long long* prof) {
     const void* fn = s->bs == 3 ? persist3_fn(s->pk_ovf != 0, s->pd != 0)
                    : s->pd ? persist_fn_dist(prof != nullptr, a.pack)
                            : persist_fn(prof != nullptr && !s->pk_ovf, (s->tune & FEM_TUNE_PK_SC1) != 0, s->pk_ovf != 0,
-                                        (a.pack <= 4 && !(s->tune & FEM_TUNE_PK_WIDE)) ? a.pack : 0);
+                                        (a.pack <= 4 && !(s->tune & FEM_TUNE_PK_WIDE)) ? a.pack : 0, od);
     // the grid spins on inter-workgroup flags, so all G workgroups must be resident together: one per CU is
     // what the occupancy query promised, and a cooperative launch makes the runtime guarantee it (or fail) even
     // when other streams / processes hold CUs. A plain launch (the bench's fixed-iteration runs) relies on the
@@ -4655,6 +4757,10 @@ void fem_pcg_destroy(fem_pcg* s) {
     pool_free(s->pk_part, s->stream);
     pool_free(s->pk_sync, s->stream);
     pool_free(s->pk_v, s->stream);
+    pool_free(s->pk_ovals, s->stream);
+    pool_free(s->pk_oucol, s->stream);
+    pool_free(s->pk_kd, s->stream);
+    pool_free(s->pk_diag, s->stream);
     pool_free(s->gv_buf, s->stream);
     pool_free(s->u2_sync, s->stream);
     pool_free(s->st, s->stream);

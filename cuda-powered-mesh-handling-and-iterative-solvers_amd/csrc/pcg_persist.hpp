@@ -214,7 +214,20 @@ struct PkArgs {
                             // never waits on L (lo >= 0 with lo == hi: L raises its flag in Q, no rows)
     const double* b;        // init launch: r0 = b - A x0 over the own rows (x0 global-length, the same on every rank)
     int init;
+    // OD build (FEM_TUNE_PK_OFFDIAG): vals / ucol are the context's diagonal-free stream (k_sell_offdiag, the list
+    // index of each slice's diagonal inside ucol), diag the dense diagonal
+    const double* diag;
+    const double* vals_full;   // the shared values and lists: the overflow slices of the OVF build read these
+    const int16_t* ucol_full;
 };
+
+// a product rounded on its own: the empty asm keeps the compiler from contracting it into a later add (an fma of
+// its two factors rounds once, not twice, and changes the bits)
+__device__ __forceinline__ double pk_mul_rn(double a, double b) {
+    double m = a * b;
+    asm("" : "+v"(m));
+    return m;
+}
 
 // DIST grid barrier with the rank exchange folded in. Arrivals as in pk_barrier (group counter, the last of a group
 // adds to ONE top counter); the add on the top counter that returns e * 8 - 1 tells its workgroup that the whole
@@ -331,9 +344,14 @@ __device__ __forceinline__ void pk_publish_flag(const PkArgs& a, int Lg, unsigne
 // their CG state in HBM (the r, p, s, x, u, w arrays, v in a.v) and are streamed every iteration like the deferred
 // schedule's rows, inside the same launch and the same barriers
 // DIST: see PkArgs (GSC1 and !OVF implied)
-template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false>
+// OD: the SpMV streams the context's diagonal-free values (sell_pair.hpp k_sell_offdiag). The diagonal of the register
+// slots' rows sits in registers (dg[], loaded once per launch) where the other builds keep their own u (uo[]): that u
+// is w r, re-formed from w (LDS) and r (registers) as the same rounded product wherever it is needed (pk_mul_rn), so
+// the diagonal term costs no load and no gather, and every iterate keeps its bits.
+template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false, bool OD = false>
 __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
     static_assert(!DIST || (GSC1 && !OVF), "distributed persistent PCG: sc1 gathers, no overflow build");
+    static_assert(!(DIST && OD), "distributed persistent PCG: no diagonal-free stream");
     unsigned long long pacc[PROF ? PK_NPROF : 1] = {};
     unsigned long long pt = 0, wspmv = 0;
     if constexpr (PROF) pt = __builtin_amdgcn_s_memtime();
@@ -407,7 +425,11 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
     unsigned ebase = st->pk_epoch;         // barriers of earlier launches (sync words count on from there)
     unsigned elast = ebase;                // last barrier epoch of this launch
 
-    double rr[MAXS], pp[MAXS], ss[MAXS], vv[MAXS], uo[MAXS];
+    double rr[MAXS], pp[MAXS], ss[MAXS], vv[MAXS];
+    double uo[OD ? 1 : MAXS];   // own u (OD: re-formed from w and r, see PK_UO)
+    double dg[OD ? MAXS : 1];   // OD: diagonal of the slot's row
+// own u of slot j: u = w r is how every u was formed (k_cg1_init, the update)
+#define PK_UO(j) (OD ? pk_mul_rn(wl[(j) * 64], rr[j]) : uo[OD ? 0 : (j)])
 #pragma unroll
     for (int j = 0; j < MAXS; ++j) {
         const unsigned row = rb + 64u * j;
@@ -420,7 +442,8 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
         if (j < PK_VL) vl[j * 64] = 0.0;
         const double wj = on ? a.w[row] : 0.0;
         wl[j * 64] = wj;
-        uo[j] = wj * rr[j];   // u = w r is how every u was formed (k_cg1_init, the update): bit-identical, no load
+        if constexpr (OD) dg[j] = on ? a.diag[row] : 0.0;
+        else uo[j] = wj * rr[j];   // bit-identical to the stored u, no load
     }
     // clamped to the flag array (nranks * G workgroups): a window is never an index outside it, whatever the
     // array holds; a window outside it is reported (FEM_PCG_BAD_WINDOW, every spinner released), not run
@@ -458,7 +481,7 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
                     ss[j] = 0.0;
                     xl[j * 64] = on ? a.x[row] : 0.0;
                     const double ui = wj * rv;
-                    uo[j] = ui;
+                    if constexpr (!OD) uo[j] = ui;
                     gp += rv * ui;
                     if (on) {
                         __hip_atomic_store(a.u + row, ui, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -559,11 +582,16 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
             const double* uvp = pk_launder(a.u);
             const int32_t* uop = a.uoff ? pk_launder(a.uoff) : nullptr;
             const int16_t* ucp = a.uoff ? pk_launder(a.ucol) : nullptr;
+// one slot's row sum: the full slice, or (OD) the diagonal-free one with the lane's own diagonal term
+#define PK_ROW(MODE, j)                                                                                             \
+    (OD ? sell_row_pair_od<pk_u<MAXS, PROF>(), (MODE) == 3 ? 1 : (MODE)>(s0 + (j), lane, slp, cop, vap, uvp, uop, ucp,      \
+                                       [&](double acc) { return acc + dg[OD ? (j) : 0] * PK_UO(j); })              \
+        : sell_row_pair<pk_u<MAXS, PROF>(), MODE>(s0 + (j), lane, slp, cop, vap, uvp, olo, ohi, uop, ucp))
 #define PK_SPMV(MODE)                                                                              \
     if (!rv) {                                                                                     \
         _Pragma("unroll") for (int j = 0; j < MAXS; ++j) {                                         \
             if (j < nreg) {                                                                        \
-                const double v = sell_row_pair<pk_u<MAXS, PROF>(), MODE>(s0 + j, lane, slp, cop, vap, uvp, olo, ohi, uop, ucp); \
+                const double v = PK_ROW(MODE, j);                                                  \
                 if (j < PK_VL) vl[j * 64] = v; else vv[j] = v;                                     \
             }                                                                                      \
             asm volatile("" ::: "memory");                                                         \
@@ -572,7 +600,7 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
         _Pragma("unroll") for (int jj = 0; jj < MAXS; ++jj) {                                      \
             const int j = MAXS - 1 - jj;                                                           \
             if (j < nreg) {                                                                        \
-                const double v = sell_row_pair<pk_u<MAXS, PROF>(), MODE>(s0 + j, lane, slp, cop, vap, uvp, olo, ohi, uop, ucp); \
+                const double v = PK_ROW(MODE, j);                                                  \
                 if (j < PK_VL) vl[j * 64] = v; else vv[j] = v;                                     \
             }                                                                                      \
             asm volatile("" ::: "memory");                                                         \
@@ -587,18 +615,22 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
                 PK_SPMV((GSC1 ? 1 : 0))
             }
 #undef PK_SPMV
+#undef PK_ROW
             if constexpr (PROF) {   // this wave's own SpMV time (results back: the v slots are written)
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 wspmv += __builtin_amdgcn_s_memtime() - tw0;
             }
             double dp = 0.0;
 #pragma unroll
-            for (int j = 0; j < MAXS; ++j) dp += uo[j] * (j < PK_VL ? vl[j * 64] : vv[j]);   // absent rows: uo = 0
+            for (int j = 0; j < MAXS; ++j) dp += PK_UO(j) * (j < PK_VL ? vl[j * 64] : vv[j]);   // absent rows: u = 0
             if constexpr (OVF) {   // overflow slices: v to HBM, u.v from the own u (this lane stored it last update)
                 __builtin_amdgcn_sched_barrier(0);
                 for (int q = 0; q < nov; ++q) {
                     const int sq = s0 + MAXS + q;
-                    const double v = sell_row_pair<pk_u<MAXS, PROF>(), GSC1>(sq, lane, slp, cop, vap, uvp, 0, 0, uop, ucp);
+                    // (OD: the full rows of the shared stream. A diagonal-free overflow slice would have to load its
+                    // diagonal and its own u from memory for the term -- nothing saved, and the loop then spills)
+                    const double v = sell_row_pair<pk_u<MAXS, PROF>(), GSC1>(sq, lane, slp, cop, OD ? a.vals_full : vap, uvp, 0, 0,
+                                                                             uop, OD ? a.ucol_full : ucp);
                     const int row = sq * 64 + lane;
                     if (row < nrows) {
                         a.v[row] = v;
@@ -686,7 +718,7 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
                 // branch-free over the lanes (rows past nrows hold zeros: their SpMV rows are zero padding); only
                 // the u store is masked. Exec-masked updates of the loop-carried arrays cost register copies.
                 if (j < nreg) {
-                    const double pi = uo[j] + bnew * pp[j];
+                    const double pi = PK_UO(j) + bnew * pp[j];
                     const double si = (j < PK_VL ? vl[j * 64] : vv[j]) + bnew * ss[j];
                     pp[j] = pi;
                     ss[j] = si;
@@ -696,7 +728,7 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
                     if (cg && wi == 0.0) ri = 0.0;
                     rr[j] = ri;
                     const double ui = wi * ri;
-                    uo[j] = ui;
+                    if constexpr (!OD) uo[j] = ui;
                     if (PK_ON(j)) {
                         __hip_atomic_store(ust + (rbi + 64u * j), ui, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if constexpr (DIST) {
@@ -827,6 +859,7 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
 }
 #undef PK_ON
 #undef PK_MARK
+#undef PK_UO
 
 // empty gather windows before k_pk_window: lo = lo_empty, hi = -1 for every logical workgroup
 __global__ void k_pk_window_init(int G, int lo_empty, int* __restrict__ win) {

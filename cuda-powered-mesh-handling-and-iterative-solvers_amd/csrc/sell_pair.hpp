@@ -382,6 +382,165 @@ __device__ __forceinline__ double sell_row_pair_body(int64_t p0, int w, int base
     return acc;
 }
 
+// Diagonal-free value stream of the persistent schedule (FEM_TUNE_PK_OFFDIAG), private to one solver context. A
+// slice-uniform slice whose delta list holds delta 0 at list index kd stores its other w - 1 list entries, in list
+// order, lane-paired as a slice of width w - 1 at the slice's own base (slice_ptr is kept, so one pointer array
+// serves both streams and the slice's last 512-byte row is simply never read); its delta list without the 0 sits at
+// the slice's uoff in a second list array, so delta pairs line up with value pairs; the last of the slice's 2 w list
+// slots (uoff[s] + 2 w - 1, never part of a list) holds kd, so the kernel needs no further array. The row's diagonal
+// goes to the dense diag[n]. Every other slice (per-lane deltas, or a list without 0) is copied as it is: kd = -1
+// (kd[s] holds the same per slice for the host).
+// One wave per slice; ovals / oucol are read only by k_pcg_persist<.., OD = true>.
+__attribute__((unused)) static __global__ void __launch_bounds__(256) k_sell_offdiag(int64_t nslices, int64_t nrows,
+                                                             const int64_t* __restrict__ slice_ptr,
+                                                             const double* __restrict__ pvals,
+                                                             const int32_t* __restrict__ uoff,
+                                                             const int16_t* __restrict__ ucol,
+                                                             double* __restrict__ ovals, int16_t* __restrict__ oucol,
+                                                             int32_t* __restrict__ kd, double* __restrict__ diag) {
+    const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int l = threadIdx.x & 63;
+    if (s >= nslices) return;   // wave-uniform
+    const int64_t p0 = slice_ptr[s];
+    const int w = (int)((slice_ptr[s + 1] - p0) >> 6);
+    const int uo = uoff[s];
+    const int64_t row = s * 64 + l;
+    int kdv = -1;
+    if (uo >= 0) {   // w <= SU_MAXW = 64: one list entry per lane
+        const unsigned long long z = __ballot(l < w && ucol[uo + l] == 0);
+        if (z) kdv = __builtin_ctzll(z);
+    }
+    if (l == 0) {
+        kd[s] = kdv;
+        if (uo >= 0) oucol[uo + 2 * w - 1] = (int16_t)kdv;
+    }
+    if (kdv < 0) {
+        for (int k = 0; k < w; ++k) ovals[p0 + 64 * k + l] = pvals[p0 + 64 * k + l];
+        if (uo >= 0)
+            for (int k = l; k < w; k += 64) oucol[uo + k] = ucol[uo + k];
+        if (row < nrows) diag[row] = 0.0;
+        return;
+    }
+    diag[row] = pvals[p0 + pair_pos(kdv, w, l)];   // a uniform slice is full: row < nrows
+    const int w1 = w - 1, np1 = w1 >> 1;
+    double2* o2 = reinterpret_cast<double2*>(ovals + p0) + l;
+    for (int j = 0; j < np1; ++j) {
+        const int k0 = 2 * j + (2 * j >= kdv), k1 = 2 * j + 1 + (2 * j + 1 >= kdv);
+        o2[64 * j] = double2{pvals[p0 + pair_pos(k0, w, l)], pvals[p0 + pair_pos(k1, w, l)]};
+    }
+    if (w1 & 1) ovals[p0 + (int64_t)np1 * 128 + l] = pvals[p0 + pair_pos(w1 - 1 + (w1 - 1 >= kdv), w, l)];
+    for (int k = l; k < w1; k += 64) oucol[uo + k] = ucol[uo + k + (k >= kdv)];
+}
+
+// plain SELL values rebuilt from the diagonal-free stream and diag (test-only: fem_pcg_debug_offdiag): k_sell_sl_unpair
+// with the list position mapped through kd. ucol is the FULL list of the shared layout.
+__attribute__((unused)) static __global__ void __launch_bounds__(256) k_sell_od_unpair(int64_t nslices,
+                                                               const int64_t* __restrict__ slice_ptr,
+                                                               const int16_t* __restrict__ cin,
+                                                               const int32_t* __restrict__ uoff,
+                                                               const int16_t* __restrict__ ucol,
+                                                               const int32_t* __restrict__ kd,
+                                                               const double* __restrict__ diag,
+                                                               const int32_t* __restrict__ rowptr, int64_t nrows,
+                                                               const double* __restrict__ ovals,
+                                                               double* __restrict__ vout) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nslices * 64;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t s = t >> 6;
+        const int l = (int)(t & 63);
+        const int64_t p0 = slice_ptr[s];
+        const int w = (int)((slice_ptr[s + 1] - p0) >> 6);
+        const int64_t row = s * 64 + l;
+        const int len = row < nrows ? rowptr[row + 1] - rowptr[row] : 0;
+        const int uo = uoff[s];
+        const int kdv = kd[s];
+        int u = 0;
+        for (int k = 0; k < w; ++k) {
+            double v = 0.0;
+            if (k < len) {
+                int pos = k;
+                if (uo >= 0) {
+                    const int d = cin[p0 + 64 * k + l];
+                    while (u < w && (int)ucol[uo + u] < d) ++u;
+                    pos = u++;
+                }
+                if (kdv < 0) v = ovals[p0 + pair_pos(pos, w, l)];
+                else if (pos == kdv) v = diag[row];
+                else v = ovals[p0 + pair_pos(pos - (pos > kdv), w - 1, l)];
+            }
+            vout[p0 + 64 * k + l] = v;
+        }
+    }
+}
+
+// y_row of one slice-uniform slice row in the diagonal-free stream: the w1 streamed list entries in list order, with
+// the row's diagonal term (diagonal times own u, both held by the lane) added by acc = diag(acc), which must be
+// `acc + d * u` like the streamed terms; it is called only where the term belongs, so what it forms or loads occupies
+// no registers while the slice's loads are in flight. The term goes where the full list had
+// delta 0, i.e. before streamed entry kd (wave-uniform; kd = w1: after the last; kd < 0: a uniform slice that kept
+// its full rows, nothing inserted). Every term is `acc += a * b` like the streamed ones, so the row sum is the one
+// sell_row_pair_body<.., UNI = true> forms on the full slice, bit for bit.
+template <int U, int SC1, class Diag>
+__device__ __forceinline__ double sell_row_pair_od_body(int64_t p0, int w1, int base, int lane,
+                                                        const int16_t* __restrict__ ucl,
+                                                        const double* __restrict__ vals, const double* __restrict__ x,
+                                                        int own_lo, int own_hi, int kd, const Diag& diag) {
+    const int np = w1 >> 1;
+    const double2* v2 = reinterpret_cast<const double2*>(vals + p0) + lane;
+    const int32_t* c2 = reinterpret_cast<const int32_t*>(ucl);
+    double acc = 0.0;
+    for (int j0 = 0; j0 < np; j0 += U) {
+        int32_t cc[U];
+        double2 vv[U];
+        double x0[U], x1[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) cc[j] = (j0 + j < np) ? c2[j0 + j] : 0;
+#pragma unroll
+        for (int j = 0; j < U; ++j) vv[j] = (j0 + j < np) ? v2[64 * (j0 + j)] : double2{0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int lo = (int)(int16_t)(cc[j] & 0xffff), hi = (int)(int16_t)(cc[j] >> 16);
+            x0[j] = (j0 + j < np) ? ldx_col<SC1>(x, base + lo, own_lo, own_hi) : 0.0;
+            x1[j] = (j0 + j < np) ? ldx_col<SC1>(x, base + hi, own_lo, own_hi) : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j)
+            if (j0 + j < np) {
+                const int k = 2 * (j0 + j);
+                if (k == kd) acc = diag(acc);
+                acc += vv[j].x * x0[j];
+                if (k + 1 == kd) acc = diag(acc);
+                acc += vv[j].y * x1[j];
+            }
+    }
+    if (w1 & 1) {
+        const int64_t t = p0 + (int64_t)np * 128 + lane;
+        const double xt = ldx_col<SC1>(x, base + (int)ucl[w1 - 1], own_lo, own_hi);
+        if (kd == w1 - 1) acc = diag(acc);
+        acc += vals[t] * xt;
+    }
+    if (kd == w1) acc = diag(acc);
+    return acc;
+}
+
+// a slice of the diagonal-free stream (k_sell_offdiag): uoff as in the shared layout, ucol the private lists, kd read
+// from the slice's list slot 2 w - 1
+template <int U, int SC1, class Diag>
+__device__ __forceinline__ double sell_row_pair_od(int64_t s, int lane, const int64_t* __restrict__ slice_ptr,
+                                                   const int16_t* __restrict__ cols, const double* __restrict__ vals,
+                                                   const double* __restrict__ x, const int32_t* __restrict__ uoff,
+                                                   const int16_t* __restrict__ ucol, const Diag& diag) {
+    const int64_t p0 = slice_ptr[s];
+    const int w = (int)((slice_ptr[s + 1] - p0) >> 6);
+    const int base = (int)(s * 64 + lane);
+    const int uo = __builtin_amdgcn_readfirstlane(uoff[s]);
+    if (uo >= 0) {
+        const int kdv = __builtin_amdgcn_readfirstlane((int)ucol[uo + 2 * w - 1]);
+        return sell_row_pair_od_body<U, SC1>(p0, w - (kdv >= 0), base, lane, ucol + uo, vals, x, 0, 0, kdv, diag);
+    }
+    return sell_row_pair_body<U, SC1, false>(p0, w, base, lane, cols, nullptr, vals, x, 0, 0);
+}
+
 // uoff / ucol (nullable): the slice-uniform deltas of k_sell_uniform
 template <int U, int SC1 = 0>
 __device__ __forceinline__ double sell_row_pair(int64_t s, int lane, const int64_t* __restrict__ slice_ptr,

@@ -1298,6 +1298,21 @@ class PcgRunner:
         [s_begin, s_end) of the context's matrix copy (after start())."""
         return uniform_slices(self.lib, self.h, s_begin, s_end)
 
+    def offdiag_slices(self):
+        """(slices whose diagonal the persistent launches keep on chip, slices, value bytes left out per iteration)
+        of the started context (include/fem355.h FEM_TUNE_PK_OFFDIAG); zeros when it reads the full values."""
+        c, n, nb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        C.check(self.lib.fem_pcg_offdiag_slices(self.h, ctypes.byref(c), ctypes.byref(n), ctypes.byref(nb)),
+                "fem_pcg_offdiag_slices")
+        return c.value, n.value, nb.value
+
+    def debug_offdiag_values(self):
+        """Test-only: the plain SELL values rebuilt from the started context's diagonal-free stream and diagonal."""
+        A = self.A
+        out = torch.empty(max(A.g.sell_entries, 1), dtype=F64, device=A.device)
+        C.check(self.lib.fem_pcg_debug_offdiag(self.h, C.ptr(A.g.rowptr), C.ptr(out)), "fem_pcg_debug_offdiag")
+        return out
+
     def pipelined(self):
         """True when the started context runs the pipelined persistent iteration (tune |= TUNE_PK_GV; bs = 1, single
         GPU, PCG mode, at most 2 slices per wave -- include/fem355.h FEM_TUNE_PK_GV)."""

@@ -456,6 +456,14 @@ int fem_pcg_get_schedule(fem_pcg* s);
  * SpMV over those slices reads (padding included) */
 int fem_pcg_uniform_slices(fem_pcg* s, int64_t s_begin, int64_t s_end, int64_t* uniform, int64_t* nslices,
                            int64_t* index_bytes);
+/* [sync] after fem_pcg_start: the slices whose diagonal the persistent launches keep on chip (FEM_TUNE_PK_OFFDIAG),
+ * the slice count, and the value bytes one iteration therefore does not read (8 per row of such a slice); zeros for
+ * a context that reads the full values. Overflow build: its overflow slices read the full rows and are not counted */
+int fem_pcg_offdiag_slices(fem_pcg* s, int64_t* od_slices, int64_t* nslices, int64_t* bytes);
+/* [sync, debug, test-only] the plain SELL values (slice_ptr[nslices] doubles, device) rebuilt from the started
+ * context's diagonal-free stream and its dense diagonal; rowptr: the pattern's CSR row pointers (device, int32).
+ * FEM_EARG when the context reads no such stream */
+int fem_pcg_debug_offdiag(fem_pcg* s, const int32_t* rowptr, double* vals);
 /* ------------------------------------------------------------------ solver layout
  * The matrix stored straight in the layout the PCG schedules read, so a solve converts nothing and the matrix is
  * resident once. bs = 1: lane-paired SELL entries (entry k of lane l of a slice of width w at 128 (k / 2) + 2 l + k % 2,
@@ -547,14 +555,23 @@ int fem_enforce_constraints(double* x, double* r, int64_t n, int order, int64_t 
                             int64_t G, const int64_t* r3_ptr, const int64_t* r3_master, const double* r3_wsum,
                             const int64_t* r3_slave, const double* r3_w, fem_stream_t stream);
 /* tuning flags (default FEM_TUNE_REVERSE | FEM_TUNE_PAIR | FEM_TUNE_PK_SC1 | FEM_TUNE_PK_PACK | FEM_TUNE_PK_UNI |
- * FEM_TUNE_UPD1): the SpMV of every schedule sweeps each XCD's slice range backwards on
+ * FEM_TUNE_UPD1 | FEM_TUNE_PK_OFFDIAG): the SpMV of every schedule sweeps each XCD's slice range backwards on
  * odd iterations, so the matrix tail read last (still in the MI355X's 256 MB memory-side cache) is read first by
  * the next sweep: 67 -> 57 us per SpMV on the 10M Poisson matrix. Results depend on the flags only through the
  * order of the per-block p.q partials (deterministic for a given flag set). */
 enum { FEM_TUNE_REVERSE = 1, FEM_TUNE_PAIR = 2, FEM_TUNE_PK_SC1 = 4, FEM_TUNE_PK_PACK = 8, FEM_TUNE_C1F = 16,
        FEM_TUNE_PK_COOP = 32, FEM_TUNE_DIST_FINE = 64, FEM_TUNE_PK_UNI = 128, FEM_TUNE_PK_WIDE = 256,
        FEM_TUNE_DIST_DROP = 512, FEM_TUNE_UPD1 = 1024, FEM_TUNE_U2_HOLD = 2048, FEM_TUNE_U2_SMALL = 4096,
-       FEM_TUNE_MF_GATHER = 8192, FEM_TUNE_PK_GV = 16384 };
+       FEM_TUNE_MF_GATHER = 8192, FEM_TUNE_PK_GV = 16384, FEM_TUNE_PK_OFFDIAG = 32768 };
+/* FEM_TUNE_PK_OFFDIAG (default): persistent schedule, bs = 1, single GPU, not the pipelined build -- fem_pcg_start
+ * writes a context-private copy of the paired values in which every slice-uniform slice whose delta list holds 0
+ * leaves its diagonal out (width w - 1 at the slice's own slice_ptr base, sell_pair.hpp k_sell_offdiag), and the
+ * dense diagonal beside it. The kernel keeps each row's diagonal in registers in place of the row's own u, which it
+ * re-forms as the rounded product w r, and adds the diagonal term at its list position: 8 bytes and one gather per
+ * row and iteration less, the same products in the same order, bit-identical iterates. The shared solver layout and
+ * every other reader of it are untouched; slices with per-lane deltas keep their full rows, and so do the overflow
+ * slices of the overflow build (their state is in memory: the term would cost two loads to save one).
+ * fem_pcg_offdiag_slices reports what the started context left out. */
 /* FEM_TUNE_PK_GV (opt-in, set before fem_pcg_start): persistent schedule, bs = 1, single GPU, PCG mode, systems of at
  * most 2 slices per wave (~2M rows on 256 CUs: the 1M-tet cube, a rank share of the 10M one) -- the pipelined
  * (Ghysels-Vanroose) Jacobi-PCG, whose grid reduction runs under the next SpMV (csrc/pcg_persist_gv.hpp). Its
