@@ -33,6 +33,8 @@ TUNE_DEFAULT = 1 | 2 | 4 | 8 | 128 | TUNE_UPD1 | TUNE_PK_OFFDIAG
 KIND_ELASTIC, KIND_POISSON, KIND_MASS = 0, 1, 2
 ISO_SUM, ISO_STACK, ISO_VOLUME, ISO_MASS = 0, 1, 2, 3
 MASS_SELL, MASS_DIAG = 0, 1   # include/fem355.h fem_mass_form
+MAT_SVK, MAT_NEO_HOOKEAN = 0, 1   # include/fem355.h FEM_MAT_*
+MATERIALS = {"svk": MAT_SVK, "neo_hookean": MAT_NEO_HOOKEAN}
 MODAL_OUT_GM, MODAL_OUT_NORMS, MODAL_OUT_LEN = 576, 1152, 1168   # include/fem355.h FEM_MODAL_OUT_*
 
 _P = ctypes.c_void_p
@@ -201,6 +203,8 @@ SIGNATURES = {
     "fem_newmark_update": (_I, [_L, ctypes.POINTER(_D), _I, _P, _P, _P, _P, _P, _P, _P]),
     "fem_transient_work_len": (_L, []),
     "fem_quadform_km": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "fem_tet4_nl": (_I, [_P, _P, _L, _P, _D, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fem_tet4_nl_gather": (_I, [_P, _P, _P, _L, _P, _D, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -816,6 +816,111 @@ def compute_c3d4_shared_face_forces_sum(shared_face_indices, element_forces, dev
     return out.to(device=torch.device(device), dtype=out_dtype)
 
 
+# ============================================================================ nonlinear c3d4 (csrc/nonlinear.hip)
+# Total-Lagrangian hyperelasticity of P1 tets: the K(u) and internal forces a caller of the reference's
+# newton_raphson_solver (`solver/solver.py:978-1065`) has to supply, for St. Venant-Kirchhoff ("svk") and compressible
+# neo-Hooke ("neo_hookean") materials (include/fem355.h fem_tet4_nl).
+def _material(material):
+    if material not in C.MATERIALS:
+        raise ValueError(f"Unknown material {material!r} (supported: {', '.join(sorted(C.MATERIALS))}).")
+    return C.MATERIALS[material]
+
+
+def _tet4_nl(coords, elements, displacement, E, nu, material, device, want, packed=False, check=True):
+    """One fem_tet4_nl launch -> dict of the fp64 device outputs named in `want` (of "Kt", "fe", "we", "sigma",
+    "detF"). check: raise the singular / inverted ValueError (one device-to-host read)."""
+    mat = _material(material)
+    lib = C.lib()
+    dev, coords, elements = _prep(coords, elements, device)
+    if elements.dim() != 2 or elements.shape[1] != 4:
+        raise ValueError(f"c3d4 expects 4 nodes per element, got {list(elements.shape)}")
+    u = _disp(displacement, dev, coords.shape[0])
+    M = elements.shape[0]
+    shapes = {"Kt": (M, int(lib.fem_ke_sym_stride(4))) if packed else (M, 12, 12), "fe": (M, 4, 3), "we": (M,),
+              "sigma": (M, 6), "detF": (M,)}
+    out = {k: torch.empty(shapes[k], dtype=F64, device=dev) for k in want}
+    idx = torch.full((2,), M, dtype=torch.int64, device=dev)   # (bad, inverted)
+    C.check(lib.fem_tet4_nl(C.ptr(coords), C.ptr(elements), M, C.ptr(u), float(E), float(nu), mat, 1 if packed else 0,
+                            C.ptr(out.get("Kt")), C.ptr(out.get("fe")), C.ptr(out.get("we")), C.ptr(out.get("sigma")),
+                            C.ptr(out.get("detF")), C.ptr(idx[0:1]), C.ptr(idx[1:2]), C.stream(dev)), "fem_tet4_nl")
+    if check:
+        bad, inv = (int(v) for v in idx.cpu())
+        if bad < M:
+            raise ValueError("Singular matrix encountered while computing B matrix.")
+        if inv < M:
+            raise ValueError(f"Inverted element (det F <= 0) at element {inv}.")
+    return out, (dev, elements, u)
+
+
+def compute_c3d4_tangent_K_matrix(coords, elements, displacement, E, nu, material="svk", device="cuda:0",
+                                  dtype=torch.float32):
+    """Consistent tangent stiffness [M,12,12] of geometrically nonlinear c3d4 elements at `displacement` [N,3]: the
+    Hessian of the element strain energy in its 12 dofs, exactly symmetric. Equals compute_c3d4_K_matrix at zero
+    displacement; usable wherever element matrices are (compute_nodal_forces, the solvers). ValueError for an unknown
+    material, a degenerate reference element or an inverted element (det F <= 0)."""
+    out, _ = _tet4_nl(coords, elements, displacement, E, nu, material, device, ("Kt",))
+    return _out(out["Kt"], device, dtype)
+
+
+def _tet4_tangent_sym(coords, elements, displacement, E, nu, material="svk", device="cuda:0"):
+    """compute_c3d4_tangent_K_matrix in the packed symmetric form of `_solid_ke_sym` ([M, fem_ke_sym_stride(4)] fp64 on
+    the device, for SellMatrix.add_element_matrices_sym); the upper blocks are the full matrix's bit for bit."""
+    out, _ = _tet4_nl(coords, elements, displacement, E, nu, material, device, ("Kt",), packed=True)
+    return out["Kt"]
+
+
+def compute_c3d4_internal_forces(coords, elements, displacement, E, nu, material="svk", device="cuda:0",
+                                 dtype=torch.float32):
+    """Nodal internal forces [N,3] of the deformed mesh (the gradient of the total strain energy), the element forces
+    summed per node in ascending element order (deterministic)."""
+    out, (dev, el, u) = _tet4_nl(coords, elements, displacement, E, nu, material, device, ("fe",))
+    N = u.shape[0]
+    inc_ptr, inc = cached_incidence(el, N)
+    fint = torch.empty((N, 3), dtype=F64, device=dev)
+    C.check(C.lib().fem_tet4_nl_gather(C.ptr(out["fe"]), C.ptr(inc_ptr), C.ptr(inc), N, None, 0.0, None, C.ptr(fint),
+                                       None, C.stream(dev)), "fem_tet4_nl_gather")
+    return _out(fint, device, dtype)
+
+
+def compute_c3d4_strain_energy(coords, elements, displacement, E, nu, material="svk", device="cuda:0",
+                               dtype=torch.float32):
+    """Strain energy V W(F) of every element -> [M]."""
+    out, _ = _tet4_nl(coords, elements, displacement, E, nu, material, device, ("we",))
+    return _out(out["we"], device, dtype)
+
+
+def compute_c3d4_cauchy_stress(coords, elements, displacement, E, nu, material="svk", device="cuda:0",
+                               dtype=torch.float32):
+    """Cauchy stress J^-1 P F^T of every element in Voigt order [M,6] (xx, yy, zz, xy, yz, xz): the input of
+    compute_stress_tensor, whose result feeds compute_von_mises_stress."""
+    out, _ = _tet4_nl(coords, elements, displacement, E, nu, material, device, ("sigma",))
+    return _out(out["sigma"], device, dtype)
+
+
+def compute_c3d4_deformation_gradient(coords, elements, displacement, device="cuda:0", dtype=torch.float32):
+    """(F [M,3,3] = I + sum_a u_a (x) g_a, det F [M]) from the c3d4 gradients of fem_tet4_geom; ValueError on a
+    degenerate reference element. An inverted element is reported through det F <= 0, not raised."""
+    lib = C.lib()
+    dev, coords, elements = _prep(coords, elements, device)
+    u = _disp(displacement, dev, coords.shape[0])
+    M = elements.shape[0]
+    grads = torch.empty((M, 4, 3), dtype=F64, device=dev)
+    bad = _bad_scalar(dev, M)
+    C.check(lib.fem_tet4_geom(C.ptr(coords), C.ptr(elements), M, None, C.ptr(grads), None, C.ptr(bad), C.stream(dev)),
+            "fem_tet4_geom")
+    _raise_if_singular(bad, M)
+    Fm = torch.eye(3, dtype=F64, device=dev) + torch.einsum("mai,maj->mij", u[elements], grads)
+    det = (Fm[:, 0, 0] * (Fm[:, 1, 1] * Fm[:, 2, 2] - Fm[:, 1, 2] * Fm[:, 2, 1])
+           + Fm[:, 0, 1] * (Fm[:, 1, 2] * Fm[:, 2, 0] - Fm[:, 1, 0] * Fm[:, 2, 2])
+           + Fm[:, 0, 2] * (Fm[:, 1, 0] * Fm[:, 2, 1] - Fm[:, 1, 1] * Fm[:, 2, 0]))
+    return _out(Fm, device, dtype), _out(det, device, dtype)
+
+
+__all__ += [
+    "compute_c3d4_tangent_K_matrix", "compute_c3d4_internal_forces", "compute_c3d4_strain_energy",
+    "compute_c3d4_cauchy_stress", "compute_c3d4_deformation_gradient",
+]
+
 __all__ += [
     "compute_stress_tensor", "compute_von_mises_stress", "compute_element_stress", "compute_c3d4_element_stress",
     "compute_c3d8_element_stress", "compute_c3d6_element_stress", "compute_c3d10_element_stress",

@@ -655,5 +655,195 @@ def transient_solver(K, M, elements, F, fixed, num_nodes, dt, steps, amplitude=N
         integ.close()
     return ret + (res,) if return_info else ret
 
+
+# ============================================================================ nonlinear statics
+# Large-displacement statics of c3d4 meshes: Newton's method on the total-Lagrangian residual with the hyperelastic
+# tangent of csrc/nonlinear.hip, the matrix refilled in place every iteration (system.NewtonStatics).
+# The reference's own newton_raphson_solver (`solver/solver.py:978-1065`, secant form on a caller's K(u)) follows.
+_LS_HALVINGS = 10
+_LS_C1 = 1e-4
+
+
+def _check_nonlinear(what, coords, elements, F, fixed, material, load_steps, tol, atol, max_iter, linear_rtol,
+                     linear_max_iter, u_init):
+    """Every ValueError of nonlinear_static_solver -- before any device call. Returns the fixed node ids."""
+    if not torch.is_tensor(coords) or coords.dim() != 2 or coords.shape[1] != 3:
+        raise ValueError(f"{what}: coords must be [N, 3], got {tuple(getattr(coords, 'shape', ()))}")
+    N = coords.shape[0]
+    if not torch.is_tensor(elements) or elements.dim() != 2 or elements.shape[1] != 4:
+        raise ValueError(f"{what}: c3d4 connectivity [M, 4] expected, got {tuple(getattr(elements, 'shape', ()))}")
+    if elements.numel() and (int(elements.min()) < 0 or _max_node(elements) > N):
+        raise ValueError(f"{what}: the mesh references a node outside [0, {N})")
+    if not torch.is_tensor(F) or tuple(F.shape) != (N, 3):
+        raise ValueError(f"{what}: F must be [{N}, 3], got {tuple(getattr(F, 'shape', ()))}")
+    if u_init is not None and (not torch.is_tensor(u_init) or tuple(u_init.shape) != (N, 3)):
+        raise ValueError(f"{what}: u_init must be [{N}, 3]")
+    if material not in C.MATERIALS:
+        raise ValueError(f"{what}: unknown material {material!r} (supported: {', '.join(sorted(C.MATERIALS))})")
+    if int(load_steps) < 1:
+        raise ValueError(f"{what}: load_steps must be >= 1, got {load_steps}")
+    if int(max_iter) < 1 or int(linear_max_iter) < 1:
+        raise ValueError(f"{what}: max_iter and linear_max_iter must be >= 1")
+    if not float(tol) >= 0.0 or not float(atol) >= 0.0 or not float(linear_rtol) > 0.0:
+        raise ValueError(f"{what}: tol and atol must be >= 0 and linear_rtol > 0")
+    return _fixed_ids(what, fixed, N)
+
+
+def _newton_statics_loop(ns, Fd, u, load_steps, tol, atol, max_iter, linear_rtol, linear_max_iter, on_iteration=None):
+    """The load-stepped Newton iteration of nonlinear_static_solver on a system.NewtonStatics -> NonlinearResult (u
+    left on the device). on_iteration(dict): per-iteration record hook of tools/bench_nonlinear.py."""
+    free = ns.mask == 0
+    stop = max(float(tol) * float(torch.linalg.vector_norm(Fd[free])), float(atol))
+    res = _sys.NonlinearResult(u, False, _sys.NL_OK, "", [], [], [], [])
+    S = int(load_steps)
+    for s in range(1, S + 1):
+        lf = s / S
+        print(f"Load step {s}/{S}")
+        norms, pits, alphas = [], [], []
+        res.newton_iterations.append(0)
+        res.residual_norms.append(norms)
+        res.pcg_iterations.append(pits)
+        res.step_lengths.append(alphas)
+        done = False
+        for k in range(1, int(max_iter) + 1):
+            r, en, rn, inv = ns.evaluate(u, lf, Fd, tangent=True)
+            if inv is not None:   # only a caller's u_init can be inverted here: trial points are rejected below
+                en = float("inf")
+            print(f"Iteration {k}, Residual Norm: {rn}")
+            norms.append(rn)
+            if inv is None and rn <= stop:
+                print(f"Converged after {k} iterations.")
+                done = True
+                break
+            pot = en - lf * ns.work
+            ns.tangent()
+            w = ns.jacobi()
+            delta, it, stt = ns.solve_increment(r, w, linear_rtol, linear_max_iter)
+            slope = float(torch.dot(r, delta))
+            if stt in (C.PCG_BREAKDOWN, C.PCG_ALPHA_NAN, C.PCG_BETA_NAN) or not slope > 0.0 or slope == float("inf"):
+                delta = w * r   # preconditioned steepest descent: an indefinite tangent gave no descent direction
+                slope = float(torch.dot(r, delta))
+            pits.append(it)
+            if not slope > 0.0 or slope == float("inf"):
+                res.status = _sys.NL_LINEAR_SOLVE_FAILED
+                res.message = f"No descent direction at load step {s}, iteration {k} (PCG status {stt})."
+                print(res.message)
+                res.u = u
+                return res
+            delta = delta.clone()
+            alpha, accepted, evals = 1.0, False, 0
+            for _ in range(_LS_HALVINGS + 1):
+                ut = u + alpha * delta
+                _, en_t, rn_t, inv_t = ns.evaluate(ut, lf, Fd, tangent=False)
+                evals += 1
+                if inv_t is None and (en_t - lf * ns.work <= pot - _LS_C1 * alpha * slope or rn_t < rn):
+                    accepted = True
+                    break
+                alpha *= 0.5
+            if on_iteration is not None:
+                on_iteration({"step": s, "iteration": k, "residual": rn, "pcg_iterations": it, "pcg_status": stt,
+                              "line_search_evaluations": evals, "alpha": alpha if accepted else 0.0})
+            if not accepted:
+                res.status = _sys.NL_LINE_SEARCH_FAILED
+                res.message = (f"Line search failed at load step {s}, iteration {k}: no step length down to "
+                               f"{alpha * 2.0:.3e} reduced the potential or the residual.")
+                print(res.message)
+                res.u = u
+                return res
+            u = ut
+            alphas.append(alpha)
+            res.newton_iterations[-1] = k
+        if not done:
+            print("Newton-Raphson did not converge within the maximum number of iterations.")
+            res.status = _sys.NL_MAX_ITER
+            res.message = f"Load step {s} did not converge within {int(max_iter)} iterations."
+            res.u = u
+            return res
+    res.u = u
+    res.converged = True
+    return res
+
+
+def nonlinear_static_solver(coords, elements, F, fixed, E, nu, material="svk", load_steps=1, tol=1e-8, atol=0.0,
+                            max_iter=25, linear_rtol=1e-6, linear_max_iter=10000, u_init=None, device="cuda:0",
+                            dtype=torch.float64, return_info=False):
+    """Large-displacement statics of a c3d4 mesh: u [N, 3] with f_int(u) = F, the nodes `fixed` held at zero, for the
+    hyperelastic materials of compute_c3d4_tangent_K_matrix ("svk", "neo_hookean"). The load is applied in `load_steps`
+    equal steps; each step runs Newton's method from the previous step's u:
+      1. r = load factor * F - f_int(u) on the free dofs; stop when ||r||_2 <= max(tol ||F_free||_2 (full load), atol);
+      2. the tangent is assembled in place (system.NewtonStatics) and K_T delta = r solved by Jacobi-PCG to
+         sqrt(r.z) <= linear_rtol sqrt(r0.z0); a breakdown of the PCG (an indefinite tangent) or r.delta <= 0 falls back
+         to the preconditioned steepest descent delta = w o r; an iterate stopped by linear_max_iter is kept while it is
+         a descent direction;
+      3. backtracking alpha = 1, 1/2, ... (at most 10 halvings): a trial with an inverted element is rejected; one is
+         accepted when the potential Pi = internal energy - load factor * F.u falls by 1e-4 alpha r.delta or the
+         residual norm falls (near convergence the predicted decrease is below the rounding of Pi).
+    Prints `Load step s/S`, `Iteration k, Residual Norm: x` and `Converged after k iterations.` in the style of the
+    reference's newton_raphson_solver (`solver/solver.py:1012-1025`). Never raises on non-convergence: the last accepted
+    u is returned and NonlinearResult.status is MAX_ITER or LINE_SEARCH_FAILED.
+    Limits: homogeneous Dirichlet conditions on whole nodes, one GPU, the assembled operator, c3d4. Out of scope:
+    non-zero prescribed displacements, arc-length control (limit points), other element types, a matrix-free tangent.
+    Returns u in `dtype` on `device`; with return_info also the system.NonlinearResult."""
+    what = "nonlinear_static_solver"
+    ids = _check_nonlinear(what, coords, elements, F, fixed, material, load_steps, tol, atol, max_iter, linear_rtol,
+                           linear_max_iter, u_init)
+    dev = _dev(device)
+    coords = coords.to(device=dev, dtype=F64).contiguous()
+    el = elements.to(device=dev, dtype=LONG).contiguous()
+    N = coords.shape[0]
+    mask = torch.zeros((N, 3), dtype=torch.uint8, device=dev)
+    mask[ids.to(dev)] = 1
+    Fd = F.to(device=dev, dtype=F64).reshape(-1).contiguous()
+    u = torch.zeros(3 * N, dtype=F64, device=dev) if u_init is None else \
+        u_init.to(device=dev, dtype=F64).reshape(-1).clone()
+    u[mask.view(-1) != 0] = 0.0
+    ns = _sys.NewtonStatics(coords, el, E, nu, material, mask.view(-1), graph=cached_graph(el, N))
+    try:
+        res = _newton_statics_loop(ns, Fd, u, load_steps, tol, atol, max_iter, linear_rtol, linear_max_iter)
+    finally:
+        ns.close()
+    res.u = res.u.view(N, 3).to(device=torch.device(device), dtype=dtype)
+    return (res.u, res) if return_info else res.u
+
+
+def newton_raphson_solver(K_func, elements, F_ext, u_init=None, tol=1e-8, max_iter=50, device="cuda:0",
+                          dtype=torch.float32):
+    """The reference's Newton-Raphson on K(u) u = F_ext (`solver/solver.py:978-1065`), same signature and semantics:
+    K_func(u [N, 3]) -> element matrices [M, d, d] on the device; F_int = K(u) u (the secant form); R = F_ext - F_int;
+    `Iteration k, Residual Norm: ||R||` is printed and the loop stops at ||R|| < tol with `Converged after k
+    iterations.`; otherwise delta from plain CG on K(u) delta = R from zero, stopped at sqrt(r.r) < tol or after 100
+    iterations (then `CG did not converge within the maximum number of iterations.` and the iterate is used), and
+    u += delta. No boundary conditions: the caller's K_func carries them. On the device K(u) is assembled in place on a
+    graph built once and the inner CG is the device PCG with unit weights (the same recurrences and stop). Arithmetic
+    is fp64; `dtype` is that of the u handed to K_func and returned."""
+    dev = _dev(device)
+    N = F_ext.shape[0]
+    el = elements.to(device=dev, dtype=LONG).contiguous()
+    Fd = F_ext.to(device=dev, dtype=F64).reshape(-1).contiguous()
+    dpn = F_ext.shape[1] if F_ext.dim() == 2 else 3
+    u = torch.zeros(N * dpn, dtype=F64, device=dev) if u_init is None else \
+        u_init.to(device=dev, dtype=F64).reshape(-1).clone()
+    A = _sys.SellMatrix(cached_graph(el, N), dpn)
+    ones = torch.ones(N * dpn, dtype=F64, device=dev)
+    for iteration in range(int(max_iter)):
+        K = K_func(u.view(N, dpn).to(dtype))
+        if _ke_dpn("newton_raphson_solver", K, el) != dpn:
+            raise ValueError(f"newton_raphson_solver: K_func returned {tuple(K.shape)} for {dpn} dofs per node")
+        A.reset().add_element_matrices(K.to(device=dev, dtype=F64), el)
+        R = Fd - A.matvec(u)
+        norm_R = float(torch.linalg.vector_norm(R))
+        print(f"Iteration {iteration + 1}, Residual Norm: {norm_R}")
+        if norm_R < tol:
+            print(f"Converged after {iteration + 1} iterations.")
+            break
+        res = A.pcg(R, None, w=ones, mode=C.MODE_PCG, tol=tol, max_iter=100)
+        if res.status != C.PCG_CONVERGED:
+            print("CG did not converge within the maximum number of iterations.")
+        u = u + res.x
+    else:
+        print("Newton-Raphson did not converge within the maximum number of iterations.")
+    return u.view(N, dpn).to(device=torch.device(device), dtype=dtype)
+
+
 # every public function runs in the scope of the device its `device` argument names (_capi.on_device)
 C.scope_module(globals())

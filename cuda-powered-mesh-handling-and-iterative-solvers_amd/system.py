@@ -485,6 +485,14 @@ class SellMatrix:
         self._plain_buf()
         self._sl_ok = False
 
+    def reset(self):
+        """Forget the values, keep the buffers: the next assembly call stores every value again (padding included),
+        into the layout a fresh matrix would take. For an operator refilled on the same pattern (NewtonStatics)."""
+        self._fresh = True
+        self._plain_ok = False
+        self._sl_ok = False
+        return self
+
     @property
     def n_rows(self):
         return self.g.n_nodes
@@ -1591,6 +1599,160 @@ class NewmarkIntegrator:
             res.energy_steps = en_steps
             res.energies = 0.5 * torch.stack(en).sum(1).cpu()
         return res
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.fem_pcg_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ============================================================================ nonlinear statics (csrc/nonlinear.hip)
+NL_OK, NL_MAX_ITER, NL_LINE_SEARCH_FAILED, NL_LINEAR_SOLVE_FAILED = "OK", "MAX_ITER", "LINE_SEARCH_FAILED", \
+    "LINEAR_SOLVE_FAILED"
+
+
+@dataclass
+class NonlinearResult:
+    """Outcome of solver.nonlinear_static_solver. The per-step lists have one entry per load step started: the Newton
+    iterations taken, and per iteration the residual norm it started from (plus the final one of a converged step),
+    the PCG iterations of its linear solve and the accepted step length."""
+    u: torch.Tensor
+    converged: bool
+    status: str                      # NL_OK / NL_MAX_ITER / NL_LINE_SEARCH_FAILED / NL_LINEAR_SOLVE_FAILED
+    message: str = ""
+    newton_iterations: list = None
+    residual_norms: list = None
+    pcg_iterations: list = None
+    step_lengths: list = None
+
+
+@_scoped
+class NewtonStatics:
+    """Device state of a geometrically nonlinear c3d4 statics solve: the graph, one bs = 3 SellMatrix that
+    every Newton iteration refills in place, the element buffers (forces, energies, packed tangent) and ONE PCG context
+    over fixed b / x / w buffers, all allocated once. With the matrix in layout A the context reads the matrix's own
+    values (fem_pcg_set_layout) and a refill needs nothing from it; with plain values its paired copy is rebuilt by every
+    fem_pcg_start, as for any solve. fixed_mask: uint8 [3 N], 1 on the dofs held at zero."""
+
+    def __init__(self, coords, elements, E, nu, material, fixed_mask, graph: Graph = None):
+        if material not in C.MATERIALS:
+            raise ValueError(f"Unknown material {material!r} (supported: {', '.join(sorted(C.MATERIALS))}).")
+        self.lib = C.lib()
+        self.device = dev = coords.device
+        self.coords = coords.to(F64).contiguous()
+        self.elements = elements.to(I64).contiguous()
+        if self.elements.dim() != 2 or self.elements.shape[1] != 4:
+            raise ValueError(f"NewtonStatics: c3d4 connectivity [M, 4] expected, got {tuple(self.elements.shape)}")
+        self.E, self.nu, self.mat = float(E), float(nu), C.MATERIALS[material]
+        self.N, self.M = self.coords.shape[0], self.elements.shape[0]
+        self.g = graph if graph is not None else build_graph(self.elements, self.N)
+        self.A = SellMatrix(self.g, 3)
+        n = 3 * self.N
+        self.mask = fixed_mask.to(device=dev, dtype=torch.uint8).contiguous().view(-1)
+        if self.mask.numel() != n:
+            raise ValueError(f"NewtonStatics: fixed_mask must hold {n} values, got {self.mask.numel()}")
+        e = lambda *s: torch.empty(s, dtype=F64, device=dev)
+        self.fe, self.we = e(max(self.M, 1), 4, 3), e(max(self.M, 1))
+        self.Kp = e(max(self.M, 1), int(self.lib.fem_ke_sym_stride(4)))
+        self.r, self.b, self.x, self.w = e(n), e(n), e(n), e(n)
+        self.idx = torch.empty(2, dtype=I64, device=dev)   # (degenerate, inverted) element words of a launch
+        self.work = 0.0        # fext . u of the last evaluate (the load's part of the potential)
+        self.launches = 0      # fem_tet4_nl launches so far
+        self.h = ctypes.c_void_p()
+        self._stream = C.stream(dev)
+        self._kp_ok = False
+
+    def _vec(self, x, what):
+        x = x.to(device=self.device, dtype=F64).contiguous().view(-1)
+        if x.numel() != 3 * self.N:
+            raise ValueError(f"NewtonStatics: {what} must hold {3 * self.N} values, got {x.numel()}")
+        return x
+
+    def evaluate(self, u, load_factor, fext, tangent=False):
+        """r = load_factor fext - f_int(u) (0 on the fixed dofs) -> (r, internal energy, ||r||_2, inverted): one
+        fem_tet4_nl launch (tangent: also the packed tangent, kept for `tangent()`), one gather, and ONE small
+        device-to-host copy for the scalars. r is this object's buffer, overwritten by the next call. inverted: the
+        lowest element with det F <= 0, or None (the energy is then +inf). The energies are summed in a fixed order."""
+        u, fext = self._vec(u, "u"), self._vec(fext, "fext")
+        self.idx.fill_(self.M)
+        C.check(self.lib.fem_tet4_nl(C.ptr(self.coords), C.ptr(self.elements), self.M, C.ptr(u), self.E, self.nu,
+                                     self.mat, 1, C.ptr(self.Kp) if tangent else None, C.ptr(self.fe), C.ptr(self.we),
+                                     None, None, C.ptr(self.idx[0:1]), C.ptr(self.idx[1:2]), self._stream),
+                "fem_tet4_nl")
+        self.launches += 1
+        self._kp_ok = bool(tangent)
+        C.check(self.lib.fem_tet4_nl_gather(C.ptr(self.fe), C.ptr(self.g.inc_ptr), C.ptr(self.g.inc), self.N,
+                                            C.ptr(fext), float(load_factor), C.ptr(self.mask), None, C.ptr(self.r),
+                                            self._stream), "fem_tet4_nl_gather")
+        s = torch.stack((self.we[: self.M].sum(), torch.dot(self.r, self.r), torch.dot(fext, u),
+                         self.idx[0].to(F64), self.idx[1].to(F64))).cpu()
+        if int(s[3]) < self.M:
+            raise ValueError("Singular matrix encountered while computing B matrix.")
+        self.work = float(s[2])
+        inv = int(s[4])
+        return self.r, float(s[0]), float(s[1]) ** 0.5, (inv if inv < self.M else None)
+
+    def tangent(self, u=None):
+        """Refill the matrix with the tangent at u (None: the packed tangent of the last evaluate(..., tangent=True)):
+        reset() + add_element_matrices_sym. Returns the SellMatrix."""
+        if u is not None or not self._kp_ok:
+            if u is None:
+                raise ValueError("NewtonStatics.tangent: no tangent evaluated yet; pass u")
+            u = self._vec(u, "u")
+            self.idx.fill_(self.M)
+            C.check(self.lib.fem_tet4_nl(C.ptr(self.coords), C.ptr(self.elements), self.M, C.ptr(u), self.E, self.nu,
+                                         self.mat, 1, C.ptr(self.Kp), None, None, None, None, C.ptr(self.idx[0:1]),
+                                         C.ptr(self.idx[1:2]), self._stream), "fem_tet4_nl")
+            self.launches += 1
+        self._kp_ok = False
+        self.A.reset()
+        if self.M:
+            self.A.add_element_matrices_sym(self.Kp[: self.M], self.elements)
+        else:
+            self.A.plain_values()
+        return self.A
+
+    def jacobi(self):
+        """Jacobi weights of the current tangent, zero on the fixed dofs."""
+        return self.A.jacobi(self.mask)
+
+    def solve_increment(self, r, w, linear_rtol=1e-6, linear_max_iter=10000, chunk=32):
+        """K_T delta = r by MODE_PCG from zero on the kept context, stopped at sqrt(r.z) <= linear_rtol sqrt(r0.z0)
+        (solve_tet4's rtol rule) -> (delta, PCG iterations, status). delta is this object's buffer."""
+        A = self.A
+        self.b.copy_(self._vec(r, "r"))
+        self.w.copy_(self._vec(w, "w"))
+        self.x.zero_()
+        bn = float(torch.sqrt(torch.dot(self.b, self.w * self.b)))
+        if not bn > 0.0:
+            return self.x, 0, C.PCG_CONVERGED
+        if not self.h:
+            plain = _schedule(False, None, 3) == SCHED_FUSED
+            C.check(self.lib.fem_pcg_create(A.g.n_nodes, 3, C.ptr(A.g.slice_ptr), C.ptr(A.g.cols),
+                                            A.solver_vals_ptr(plain), C.ptr(self.b), C.ptr(self.x), C.ptr(self.w),
+                                            C.MODE_PCG, 0.0, 1e-30, None, 0, self._stream, ctypes.byref(self.h)),
+                    "fem_pcg_create")
+            C.check(self.lib.fem_pcg_set_schedule(self.h, _schedule(False, None, 3)), "fem_pcg_set_schedule")
+            C.check(self.lib.fem_pcg_set_entries(self.h, A.g.sell_entries), "fem_pcg_set_entries")
+            A.attach_cols16(self.h)
+            A.attach_layout(self.h, plain)
+            self._ctx_sl = A.solver_layout
+        elif self._ctx_sl != A.solver_layout:   # the refill must land where the context reads
+            raise C.FemError("NewtonStatics: the matrix changed layout under its solver context")
+        elif not self._ctx_sl:
+            A.plain_values()
+        C.check(self.lib.fem_pcg_set_tol(self.h, float(linear_rtol) * bn), "fem_pcg_set_tol")
+        it, stt, rz = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+        C.check(self.lib.fem_pcg_solve(self.h, int(linear_max_iter), int(chunk), ctypes.byref(it), ctypes.byref(stt),
+                                       ctypes.byref(rz)), "fem_pcg_solve")
+        _check_sync(stt.value)
+        return self.x, it.value, stt.value
 
     def close(self):
         if getattr(self, "h", None):

@@ -872,6 +872,31 @@ int fem_quadform_km(int64_t nrows, int bs, int layout_a, const int64_t* slice_pt
                     const int16_t* dcols, const double* kvals, const double* mass, int mass_form, const double* X,
                     double* work, double* out, fem_stream_t stream);
 
+/* ------------------------------------------------------------------ nonlinear statics (csrc/nonlinear.hip)
+ * Geometrically nonlinear (total-Lagrangian) c3d4 elasticity -- the K(u) the reference's newton_raphson_solver
+ * (`solver/solver.py:978-1065`) takes from its caller, formed here for two hyperelastic materials. With the gradients
+ * g_a and volume V of fem_tet4_geom, F = I + sum_a u_a (x) g_a, J = det F, lam / mu the Lame constants of E, nu:
+ *   FEM_MAT_SVK          W = lam/2 (tr E)^2 + mu E:E, E = (F^T F - I)/2; P = F S, S = lam tr(E) I + 2 mu E
+ *   FEM_MAT_NEO_HOOKEAN  W = mu/2 (F:F - 3) - mu ln J + lam/2 (ln J)^2;  P = mu (F - F^-T) + lam ln J F^-T
+ * fem_tet4_nl: per element the consistent tangent Kt (the Hessian of V W in the element's 12 dofs; packed != 0: the
+ *   upper 3x3 blocks in fem_iso_ke_sym's layout for npe = 4, which fem_assemble_from_ke_sym consumes; else the full
+ *   [M,12,12] whose upper blocks are the packed ones bit for bit and whose lower blocks are their transposes), the
+ *   internal forces fe [M,4,3] = V P g_a, the strain energy we [M] = V W, the Cauchy stress sigma [M,6] = J^-1 P F^T in
+ *   fem_voigt_to_tensor's order (xx, yy, zz, xy, yz, xz) and detF [M]. Every output may be NULL; Kt == NULL runs a
+ *   build without the tangent work (same fe / we bits). An element with det F <= 0 writes zeros to Kt, fe, sigma, +inf
+ *   to we, its det F to detF, and lowers *inverted_idx; the other elements are unaffected. *bad_idx: as fem_tet4_ke
+ *   (|det[1 x y z]| < 1e-12; the caller raises FEM_ESINGULAR's error); such an element's outputs are those of an
+ *   inverted one with detF 0. Both index words are device int64 preset to M. M == 0: FEM_OK, no launch.
+ * fem_tet4_nl_gather: fint [N,3] = the element forces summed per node in ascending incidence order (fem_ebe_apply's
+ *   order: the same bits on every run, no atomics) and r = load_factor fext - fint, 0 where mask != 0. fint, r and mask
+ *   may be NULL. */
+enum { FEM_MAT_SVK = 0, FEM_MAT_NEO_HOOKEAN = 1 };
+int fem_tet4_nl(const double* coords, const int64_t* conn, int64_t M, const double* u, double E, double nu,
+                int material, int packed, double* Kt, double* fe, double* we, double* sigma, double* detF,
+                int64_t* bad_idx, int64_t* inverted_idx, fem_stream_t stream);
+int fem_tet4_nl_gather(const double* fe, const int32_t* inc_ptr, const int32_t* inc, int64_t N, const double* fext,
+                       double load_factor, const uint8_t* mask, double* fint, double* r, fem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

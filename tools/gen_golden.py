@@ -324,6 +324,42 @@ def gen_topology(el, so):
     save("topology", **out)
 
 
+def gen_newton_secant(el, so):
+    """The reference's own newton_raphson_solver (`solver/solver.py:978-1065`) on the CPU at fp64, on a secant
+    stiffness it accepts: K_e(u) = K0_e (1 + 4 |B_e u_e|^2) + springs of 10 on the dofs of the z = 0 face (its solver
+    takes no boundary conditions: the K_func carries them). Stored: the inputs K_func is built from, u, the captured
+    stdout and the smallest eigenvalue of the final secant matrix."""
+    coords, tets = mesh.kuhn_cube(2, jitter=0.15)
+    N, M = coords.shape[0], tets.shape[0]
+    K0 = el.compute_c3d4_K_matrix(coords, tets, 1.0, 0.3, device=CPU, dtype=F64)
+    B = el.compute_c3d4_B_matrix(coords, tets, device=CPU, dtype=F64)
+    z = coords[:, 2]
+    fixed = torch.nonzero(z == z.min()).reshape(-1)
+    top = torch.nonzero(z == z.max()).reshape(-1)
+    Ks = torch.zeros((M, 12, 12), dtype=F64)
+    for n in fixed.tolist():   # the node's springs go into the first element that holds it
+        e, a = (tets == n).nonzero()[0].tolist()
+        for c in range(3):
+            Ks[e, 3 * a + c, 3 * a + c] = 10.0
+    F = torch.zeros((N, 3), dtype=F64)
+    F[top] = torch.tensor([0.0, 0.0, 0.15], dtype=F64) / top.numel()
+    tol = 1e-9
+
+    def K_func(u):
+        eps = torch.einsum("mij,mj->mi", B, u[tets].reshape(M, 12))
+        return K0 * (1.0 + 4.0 * (eps * eps).sum(1)).view(M, 1, 1) + Ks
+
+    u, text = run_quiet(so.newton_raphson_solver, K_func, tets, F, tol=tol, device=CPU, dtype=F64)
+    Kf = K_func(u)
+    dofs = (tets.unsqueeze(-1) * 3 + torch.arange(3).view(1, 1, 3)).reshape(M, 12)
+    A = torch.zeros((3 * N, 3 * N), dtype=F64)
+    for e in range(M):
+        A[dofs[e].unsqueeze(1), dofs[e].unsqueeze(0)] += Kf[e]
+    lam_min = float(torch.linalg.eigvalsh(A)[0])
+    save("newton_secant_n2", coords=coords, tets=tets, K0=K0, B=B, Kspring=Ks, F=F, fixed=fixed, tol=np.float64(tol),
+         u=u, lam_min=np.float64(lam_min), stdout=np.array(text))
+
+
 def main():
     if not os.path.isdir(REF):
         print("reference not present; nothing to do")
@@ -331,6 +367,11 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     el, so = load_reference()
     torch.manual_seed(0)
+    only = sys.argv[1:]   # names of single generators (e.g. `newton_secant`): the other fixtures are left as they are
+    if only:
+        for name in only:
+            globals()["gen_" + name](el, so)
+        return 0
     gen_tet4_n4(el, so)
     gen_tet4_n6(el, so)
     gen_poisson(el, so)
@@ -340,6 +381,7 @@ def main():
     gen_constrained(el, so)
     gen_stress(el, so)
     gen_topology(el, so)
+    gen_newton_secant(el, so)
     return 0
 
 
