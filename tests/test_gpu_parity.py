@@ -3,11 +3,14 @@
 Tolerances (fp64): element quantities 1e-12 relative (closed-form vs LU rounding), operators 1e-12, solutions
 1e-10 relative with iteration counts within ±2 of the reference (SURVEY §8(c) contract); integer patterns
 bit-exact."""
+import ctypes
+
 import pytest
 import torch
 
 from conftest import load_golden, rel
 from oracle import ref_cpu as R
+from pattern_ref import helix_fan as _helix_fan, incidence_ref
 
 pytestmark = pytest.mark.gpu
 E, NU = 113.8e9, 0.342
@@ -253,6 +256,9 @@ def test_incidence_bucket_sort_equals_radix_sort(gpu, monkeypatch):
         ip2, in2 = system.incidence(eg, N)
         monkeypatch.delenv("FEM355_INC_RADIX", raising=False)
         assert torch.equal(ip1, ip2) and torch.equal(in1, in2), (el.shape, N)
+        ip_ref, in_ref = incidence_ref(el, N)                  # and both are the host's stable sort
+        assert torch.equal(ip1.cpu().long(), ip_ref) and torch.equal(in1.cpu().long(), in_ref), (el.shape, N)
+        assert torch.equal(ip2.cpu().long(), ip_ref) and torch.equal(in2.cpu().long(), in_ref), (el.shape, N)
     bad = torch.tensor([[0, 1, 2, 3], [1, 2, 3, 9]])
     with pytest.raises(IndexError):
         system.build_graph(bad.to(gpu), 5)
@@ -262,6 +268,8 @@ def test_pattern_wide_rows_vs_oracle(gpu):
     """Rows past every LDS tier: > 2048 candidates (c3d10 x9 repeats, hash tier) and > 512 unique neighbours
     (a fan of 700 tets around node 0, selection tier); bit-exact against the oracle, also through the CSR C-ABI."""
     _, mesh, _, system = _mods()
+    from fem355 import _capi as cap
+    lib = cap.lib()
     c10, t10 = mesh.tet10_cube(3)
     a = torch.arange(1, 701)
     fan = torch.stack([torch.zeros_like(a), a, a + 1, a + 2], 1)
@@ -271,6 +279,19 @@ def test_pattern_wide_rows_vs_oracle(gpu):
         rp, ci = R.node_pattern(t, N)
         assert torch.equal(gph.rowptr.cpu().long(), rp) and torch.equal(gph.colidx.cpu().long(), ci)
         assert torch.equal(gph.colidx.cpu().long()[gph.diagpos.cpu().long()], torch.arange(N))
+        # the dof-level CSR C-ABI (dpn 1: the node pattern itself), sizing call first
+        el = t.to(gpu).contiguous()
+        rowptr = torch.empty(N + 1, dtype=torch.int32, device=gpu)
+        nnz = ctypes.c_int64()
+        cap.check(lib.fem_csr_pattern(cap.ptr(el), el.shape[0], el.shape[1], 1, N, cap.ptr(rowptr), None, None,
+                                      ctypes.byref(nnz), cap.stream(gpu)), "fem_csr_pattern")
+        assert nnz.value == ci.numel()
+        colidx = torch.empty(nnz.value, dtype=torch.int32, device=gpu)
+        diag = torch.empty(N, dtype=torch.int32, device=gpu)
+        cap.check(lib.fem_csr_pattern(cap.ptr(el), el.shape[0], el.shape[1], 1, N, cap.ptr(rowptr), cap.ptr(colidx),
+                                      cap.ptr(diag), ctypes.byref(nnz), cap.stream(gpu)), "fem_csr_pattern")
+        assert torch.equal(rowptr.cpu().long(), rp) and torch.equal(colidx.cpu().long(), ci)
+        assert torch.equal(diag, gph.diagpos)
     assert int(rp[1] - rp[0]) == 703
 
 
@@ -1127,15 +1148,6 @@ def test_merged_update_give_up_is_all_or_nothing(gpu):
     plain = A.pcg(b, w=w, tol=tol, max_iter=5000, schedule=0, tune=cap.TUNE_DEFAULT & ~cap.TUNE_UPD1)
     assert held.status == plain.status == cap.PCG_CONVERGED and held.iterations == plain.iterations
     assert torch.equal(held.x, plain.x)
-
-
-def _helix_fan(m):
-    """m non-degenerate tets [0, a, a+1, a+2] around node 0 (a row of m + 3 columns) on a helix of nodes."""
-    th = torch.arange(1, m + 3, dtype=F64) * 0.3
-    pts = torch.stack([torch.cos(th), torch.sin(th), 0.05 * th], 1)
-    c = torch.cat([torch.zeros(1, 3, dtype=F64), pts])
-    a = torch.arange(1, m + 1)
-    return c, torch.stack([torch.zeros_like(a), a, a + 1, a + 2], 1)
 
 
 @pytest.mark.parametrize("m,gap", [(60, 0), (60, 40000), (300, 0), (300, 40000), (32700, 0), (33000, 0)])

@@ -8,6 +8,7 @@ import torch
 from conftest import rel
 from oracle import ref_cpu as R
 from oracle import rcm_ref
+from pattern_ref import helix_fan as _helix_fan
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
@@ -24,13 +25,6 @@ def _permute(c, t, seed):
     inv = torch.empty_like(perm)
     inv[perm] = torch.arange(perm.numel())
     return c[perm], inv[t]
-
-
-def _helix_fan(m):
-    th = torch.arange(1, m + 3, dtype=F64) * 0.3
-    c = torch.cat([torch.zeros(1, 3, dtype=F64), torch.stack([torch.cos(th), torch.sin(th), 0.05 * th], 1)])
-    a = torch.arange(1, m + 1)
-    return c, torch.stack([torch.zeros_like(a), a, a + 1, a + 2], 1)
 
 
 @pytest.mark.parametrize("case", ["permuted", "lexicographic", "components", "fan", "bigfan"])
