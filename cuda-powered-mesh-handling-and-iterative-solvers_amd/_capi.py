@@ -35,6 +35,7 @@ ISO_SUM, ISO_STACK, ISO_VOLUME, ISO_MASS = 0, 1, 2, 3
 MASS_SELL, MASS_DIAG = 0, 1   # include/fem355.h fem_mass_form
 MAT_SVK, MAT_NEO_HOOKEAN = 0, 1   # include/fem355.h FEM_MAT_*
 MATERIALS = {"svk": MAT_SVK, "neo_hookean": MAT_NEO_HOOKEAN}
+SHELL_LOCAL, SHELL_POINTS, SHELL_GLOBAL = 0, 1, 2   # include/fem355.h FEM_SHELL_*
 MODAL_OUT_GM, MODAL_OUT_NORMS, MODAL_OUT_LEN = 576, 1152, 1168   # include/fem355.h FEM_MODAL_OUT_*
 
 _P = ctypes.c_void_p
@@ -205,6 +206,10 @@ SIGNATURES = {
     "fem_quadform_km": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "fem_tet4_nl": (_I, [_P, _P, _L, _P, _D, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fem_tet4_nl_gather": (_I, [_P, _P, _P, _L, _P, _D, _P, _P, _P, _P]),
+    "fem_shell_ke": (_I, [_P, _P, _L, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "fem_shell_geom": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fem_shell_apply": (_I, [_P, _P, _P, _I, _P, _P, _L, _P, _P, _P]),
+    "fem_shell_stress": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

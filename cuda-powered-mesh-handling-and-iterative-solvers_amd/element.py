@@ -8,7 +8,7 @@ notebook call sites work unchanged. Differences, all deliberate:
     (there is no CPU code path in this package: see `_capi.lib()`);
   * integration-point tables are evaluated on the host exactly as the reference evaluates them (including its
     quirks: c3d10 weights summing to 0.45, the float32-rounded line points of c3d6), then handed to the kernels.
-Out of scope: shells, topology, visualisation, c3d20/c3d15.
+Shell elements live in `shell.py`. Out of scope: visualisation, c3d20/c3d15.
 """
 from __future__ import annotations
 

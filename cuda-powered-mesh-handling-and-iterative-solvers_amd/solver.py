@@ -1,8 +1,9 @@
 """Reference-compatible solver API (`solver/solver.py` of sml2004/CUDA-powered-mesh-handling-and-Iterative-
 solvers @ 2025-04-18), executed on the MI355X.
 
-Like the reference, this module re-exports the element API (`from element import *`, `solver/solver.py:1-2`),
-so `solver.compute_nodal_forces(...)` etc. resolve exactly as in the notebooks.
+Like the reference, this module re-exports the element and shell APIs (`from element import *`, `from shell import *`,
+`solver/solver.py:1-2`), so `solver.compute_nodal_forces(...)`, `solver.compute_s3_K_matrix(...)` etc. resolve exactly
+as in the notebooks.
 
 The solvers take the reference's hand-off object (element matrices K [M, d, d] + connectivity), assemble them
 once on the device into a SELL-64 global matrix (deterministic row-gather, `system.py`) and run the whole
@@ -19,6 +20,8 @@ try:
     from .element import *  # noqa: F401,F403  (the reference's `from element import *`)
     from .element import _dev, _key, cached_incidence, compute_c3d4_K_matrix, compute_c3d6_K_matrix, \
         compute_c3d8_K_matrix
+    from .shell import *  # noqa: F401,F403  (the reference's `from shell import *`)
+    from .shell import shell_global_K
     from .constraints import *  # noqa: F401,F403
     from .constraints import ConstraintSet
 except ImportError:  # pragma: no cover - flat import from the package directory
@@ -27,6 +30,8 @@ except ImportError:  # pragma: no cover - flat import from the package directory
     from element import *  # type: ignore # noqa
     from element import _dev, _key, cached_incidence, compute_c3d4_K_matrix, compute_c3d6_K_matrix, \
         compute_c3d8_K_matrix  # type: ignore
+    from shell import *  # type: ignore # noqa
+    from shell import shell_global_K  # type: ignore
     from constraints import *  # type: ignore # noqa
     from constraints import ConstraintSet  # type: ignore
 
@@ -222,11 +227,15 @@ def compute_diagonal_preconditioner(K, elements, N, device="cuda:0", dtype=torch
 def static_structure_solver(coords, force, fixed, c3d4=None, c3d6=None, c3d8=None, s3=None, s4=None, material=None,
                             u_init=None, tol=1e-10, max_iter=1000, device="cuda:0", dtype=torch.float64, eps=1e-30,
                             return_info=False):
-    """Mixed solid mesh: assemble c3d4 (`compute_c3d4_K_matrix`), c3d8 (8-point rule) and c3d6 (single point)
-    into one global operator, then stable CG with `fixed` nodes held at zero. u, force are [N, 6]; solids use
-    columns 0-2. Shells (s3/s4) are out of scope of this build."""
+    """Mixed mesh: assemble c3d4 (`compute_c3d4_K_matrix`), c3d8 (8-point rule), c3d6 (single point) and the shells
+    s3 / s4 (`compute_s3_K_matrix` / `compute_s4_K_matrix` with material['membrane'], material['bending']) into one
+    global operator, then stable CG with `fixed` nodes held at zero in all six columns. u, force are [N, 6]; solids
+    use columns 0-2, shells all six. With shells the system has 6 dofs per node on the bs = 3 matrix
+    (`system.SixDofMap`); a rotation dof of a node without a shell has no rows: it keeps its u_init value (or 0) and
+    a load on it is a ValueError. Without shells the 3-dof path below runs as before."""
     if s3 is not None or s4 is not None:
-        raise NotImplementedError("static_structure_solver: shell elements (s3/s4) are out of scope of fem355")
+        return _static_with_shells(coords, force, fixed, c3d4, c3d6, c3d8, s3, s4, material, u_init, tol, max_iter,
+                                   device, dtype, eps, return_info)
     dev = _dev(device)
     coords = coords.to(device=dev, dtype=F64).contiguous()
     force = force.to(device=dev, dtype=F64)
@@ -260,6 +269,53 @@ def static_structure_solver(coords, force, fixed, c3d4=None, c3d6=None, c3d8=Non
     if u_init is not None:
         u[:, 3:] = u_init.to(device=dev, dtype=F64)[:, 3:]
     u[:, :3] = res.x.view(N, 3)
+    u[torch.as_tensor(fixed).to(device=dev, dtype=LONG)] = 0.0
+    u = u.to(device=torch.device(device), dtype=dtype)
+    return (u, res) if return_info else u
+
+
+def _solid_families(coords, c3d4, c3d6, c3d8, material, dev):
+    """(K_e, connectivity) of the solid families present, in the reference's order c3d4, c3d8, c3d6."""
+    fams = []
+    for el, ke in ((c3d4, compute_c3d4_K_matrix), (c3d8, compute_c3d8_K_matrix), (c3d6, compute_c3d6_K_matrix)):
+        if el is not None:
+            el = el.to(device=dev, dtype=LONG).contiguous()
+            fams.append((ke(coords, el, material["E"], material["nu"], device=dev, dtype=F64), el))
+    return fams
+
+
+def _static_with_shells(coords, force, fixed, c3d4, c3d6, c3d8, s3, s4, material, u_init, tol, max_iter, device, dtype,
+                        eps, return_info):
+    """static_structure_solver with s3 and / or s4: shell K_e in the global frame, one bs = 3 matrix over the
+    translation and rotation blocks, stable CG on one context with the 6-dof free mask."""
+    dev = _dev(device)
+    coords = coords.to(device=dev, dtype=F64).contiguous()
+    force = force.to(device=dev, dtype=F64)
+    N = coords.shape[0]
+    if tuple(force.shape) != (N, 6):
+        raise ValueError(f"static_structure_solver: force must be [{N}, 6] with shell elements, got "
+                         f"{list(force.shape)}")
+    shells = [s.to(device=dev, dtype=LONG).contiguous() for s in (s3, s4) if s is not None]
+    dm = _sys.SixDofMap(N, shells)
+    if dm.rowless_load(force):
+        raise ValueError("static_structure_solver: rotational loads need shell elements on the loaded nodes")
+    fams = _solid_families(coords, c3d4, c3d6, c3d8, material, dev)
+    shell_fams = [(shell_global_K(coords, s, material["membrane"], material["bending"], device=dev)[0], s)
+                  for s in shells]
+    print("Preprocessing done.")
+    conns = [el for _, el in fams] + [dm.shell_connectivity(s) for _, s in shell_fams]
+    g = _sys.build_graph(_sys.pad_connectivity(conns, max(c.shape[1] for c in conns)), dm.n_blocks)
+    A = _sys.SellMatrix(g, 3)
+    for Ke, el in fams:
+        A.add_element_matrices(Ke, el, inc=_sys.incidence(el, dm.n_blocks))
+    for Kg, s in shell_fams:
+        A.add_shell_matrices(Kg, s, dm)
+    base = None if u_init is None else u_init.to(device=dev, dtype=F64)
+    u0 = None if base is None else dm.to_blocks(base)
+    res = A.pcg(dm.to_blocks(force), u0, w=dm.free_mask(fixed), mode=C.MODE_CG_STABLE, tol=tol, max_iter=max_iter,
+                eps=eps, schedule=_sys.SCHED_THREE)
+    _cg_messages(res, "static")
+    u = dm.from_blocks(res.x, base)
     u[torch.as_tensor(fixed).to(device=dev, dtype=LONG)] = 0.0
     u = u.to(device=torch.device(device), dtype=dtype)
     return (u, res) if return_info else u

@@ -13,7 +13,10 @@ from dataclasses import dataclass
 
 import torch
 
-from . import _capi as C
+try:
+    from . import _capi as C
+except ImportError:  # pragma: no cover - flat import from the package directory (`import solver`)
+    import _capi as C  # type: ignore
 
 I32, I64, F64 = torch.int32, torch.int64, torch.float64
 
@@ -406,6 +409,64 @@ def pad_connectivity(blocks, npe_max):
     return torch.cat(out, 0).contiguous()
 
 
+class SixDofMap:
+    """6 dofs per node on the bs = 3 matrices: every node n has a translation block n in [0, N); every node that
+    carries a shell also has a rotation block N + rank(n), rank(n) its position among the shell nodes in ascending
+    order. Dof (n, c) is scalar row 3 block + c % 3. A shell element with npe nodes is then an ordinary bs = 3 element
+    with 2 npe block-nodes [t0 .. t(npe-1), r0 .. r(npe-1)] -- the row order of fem_shell_ke's global-frame matrices
+    -- and solid families keep their node ids. Rotation dofs of a node without a shell have no rows."""
+
+    def __init__(self, n_nodes: int, shells):
+        shells = [s for s in shells if s is not None]
+        if not shells:
+            raise ValueError("SixDofMap: no shell connectivity")
+        dev = shells[0].device
+        self.device = dev
+        self.n_nodes = int(n_nodes)
+        has = torch.zeros(self.n_nodes, dtype=torch.bool, device=dev)
+        for s in shells:
+            check_connectivity(s, self.n_nodes)
+            has[s.reshape(-1)] = True
+        self.has_shell = has
+        self.shell_nodes = torch.nonzero(has).view(-1)
+        rank = torch.cumsum(has.to(I64), 0) - 1
+        self.rot_block = torch.where(has, self.n_nodes + rank, torch.full_like(rank, -1))
+        self.n_blocks = self.n_nodes + int(self.shell_nodes.numel())
+
+    def shell_connectivity(self, shell: torch.Tensor) -> torch.Tensor:
+        """[M, 2 npe] block-node connectivity of a shell family: its nodes, then their rotation blocks."""
+        shell = shell.to(device=self.device, dtype=I64)
+        return torch.cat([shell, self.rot_block[shell]], dim=1).contiguous()
+
+    def to_blocks(self, x: torch.Tensor) -> torch.Tensor:
+        """x [N, 6] -> [n_blocks, 3] (the rotation columns of nodes without a shell are left out)."""
+        x = x.to(device=self.device, dtype=F64)
+        if tuple(x.shape) != (self.n_nodes, 6):
+            raise ValueError(f"expected [{self.n_nodes}, 6], got {list(x.shape)}")
+        return torch.cat([x[:, :3], x[self.shell_nodes, 3:]], dim=0).contiguous()
+
+    def from_blocks(self, xb: torch.Tensor, base: torch.Tensor = None) -> torch.Tensor:
+        """[n_blocks, 3] -> [N, 6]; rotation columns of nodes without a shell come from `base` [N, 6] (else 0)."""
+        xb = xb.view(self.n_blocks, 3)
+        out = (torch.zeros((self.n_nodes, 6), dtype=F64, device=self.device) if base is None
+               else base.to(device=self.device, dtype=F64).clone())
+        out[:, :3] = xb[: self.n_nodes]
+        out[self.shell_nodes, 3:] = xb[self.n_nodes:]
+        return out
+
+    def free_mask(self, fixed=None) -> torch.Tensor:
+        """1 on free scalar rows, 0 on all six dofs of the `fixed` nodes -> [3 n_blocks] fp64."""
+        w = torch.ones((self.n_nodes, 6), dtype=F64, device=self.device)
+        if fixed is not None:
+            w[torch.as_tensor(fixed).to(device=self.device, dtype=I64)] = 0.0
+        return self.to_blocks(w).view(-1)
+
+    def rowless_load(self, force: torch.Tensor) -> bool:
+        """True when `force` [N, 6] loads a rotation dof that has no rows (a node without a shell)."""
+        f = force.to(device=self.device)
+        return bool((f[~self.has_shell, 3:] != 0).any())
+
+
 def uniform_slices(lib, h, s_begin=0, s_end=-1):
     """fem_pcg_uniform_slices of a solver context handle: (uniform slices, slices, column-index bytes per SpMV)."""
     u, n, ib = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
@@ -540,6 +601,16 @@ class SellMatrix:
                                              self.g.max_width if tiled else 0, C.ptr(self._vals),
                                              C.stream(self.device)), "fem_assemble_from_ke_ex2")
         return self
+
+    def add_shell_matrices(self, Ke_global: torch.Tensor, shell: torch.Tensor, dofmap: "SixDofMap"):
+        """vals += one shell family on a 6-dof system: Ke_global [M, 6 npe, 6 npe] in the global frame and block order
+        (fem_shell_ke, FEM_SHELL_GLOBAL), shell [M, npe] node ids, on this bs = 3 matrix whose rows are `dofmap`'s
+        blocks. The family goes through add_element_matrices as a bs = 3 family of 2 npe block-nodes."""
+        if self.bs != 3 or self.g.n_nodes != dofmap.n_blocks:
+            raise ValueError(f"add_shell_matrices: a bs = 3 matrix over {dofmap.n_blocks} blocks is needed "
+                             f"(bs = {self.bs}, {self.g.n_nodes} rows)")
+        conn = dofmap.shell_connectivity(shell)
+        return self.add_element_matrices(Ke_global, conn, inc=incidence(conn, dofmap.n_blocks))
 
     def add_stiffness_and_mass(self, Ke: torch.Tensor, Me: torch.Tensor, elements: torch.Tensor, mass: "SellMatrix"):
         """This bs = 3 matrix += coalesce(P_e^T K_e P_e) and the bs = 1 `mass` (same pattern object) += coalesce(P_e^T

@@ -897,6 +897,42 @@ int fem_tet4_nl(const double* coords, const int64_t* conn, int64_t M, const doub
 int fem_tet4_nl_gather(const double* fe, const int32_t* inc_ptr, const int32_t* inc, int64_t N, const double* fext,
                        double load_factor, const uint8_t* mask, double* fint, double* r, fem_stream_t stream);
 
+/* ------------------------------------------------------------------ shell elements (csrc/shell.hip)
+ * Flat s3 / s4 shells with 6 dofs per node (u, v, w, thx, thy, thz) -- the reference's `solver/shell.py`, formulation
+ * quirks included: frame unit = [a; b; c] from edge 0->1 and edge 0->2 (npe 3) / 0->3 (npe 4), local
+ * coordinates (x - x0) unit^T of which x, y are used, membrane stiffness on local (u, v), a rotation-only bending block
+ * on local (thx, thy), zero rows and columns for w and thz.
+ *   D6 [host, 6]: (D00, D01, D22) of the membrane block and (D33, D34, D55) of the bending block of the 6x6 material
+ *     matrix (compute_kirchoff_D_matrix, `:15-39`).
+ *   pts [host, 4 x 4], npe 4 only: per integration point the factors (1 - xi, 1 + xi, 1 - eta, 1 + eta) as the caller
+ *     wants them rounded (the reference's K takes the fp32-rounded 1/sqrt(3), `:651-672,840-842`; its summed B rounds
+ *     the factors themselves to fp32, `:814-815,692-704`). The weights are 1.
+ * fem_shell_ke: Ke of every element, d = 6 npe (compute_s3_K_matrix `:440-453`, compute_s4_K_matrix `:825-861`):
+ *     FEM_SHELL_LOCAL   [M, d, d] in the element's frame, rows 6 n + dof
+ *     FEM_SHELL_POINTS  [M, d, d, 4], the four points' terms (npe 4; the reference's single=False)
+ *     FEM_SHELL_GLOBAL  [M, d, d] = T^T K T, T = blockdiag(unit) per node, in the block order of the 6-dof assembly:
+ *                       rows 3 (h npe + n) + i with h = 0 the translations, h = 1 the rotations of node n
+ *   and unit [M,3,3]; Ke or unit may be NULL. A degenerate element (zero edge 0->1, a frame whose second edge is
+ *   collinear with the first to 1e-12 of its length, a zero or non-finite det J) is FEM_ESINGULAR's condition:
+ *   *bad_idx [device int64, preset to M] = the first such element, its outputs are zeros and the caller raises, as
+ *   for fem_tet4_ke. A negative det J (an inverted element) is valid and flips the sign like the reference.
+ * fem_shell_geom: at one point (pt [host, 4], npe 4) unit [M,3,3], local [M,npe,3], J [M,2,2], grads [M,npe,2],
+ *   B [M,6,d] (`:297-438`, `:599-800`); every output and bad_idx may be NULL.
+ * fem_shell_apply: y [N,6] = sum_e R_e^T K_e R_e u for local-frame Ke [M,d,d] and unit [M,3,3] -- replaces
+ *   compute_shell_nodal_forces (`:58-102`); a row gather over the node -> element incidence in ascending order, no
+ *   atomics, the same bits on every run.
+ * fem_shell_stress: nmq [M,6] = D B u_e with B summed over the points, applied to the rows of u [N,6] as they are
+ *   (compute_s3_shell_stress `:455-468`, compute_s4_shell_stress `:863-876`). */
+enum { FEM_SHELL_LOCAL = 0, FEM_SHELL_POINTS = 1, FEM_SHELL_GLOBAL = 2 };
+int fem_shell_ke(const double* coords, const int64_t* conn, int64_t M, int npe, const double* D6, const double* pts,
+                 int frame, double* Ke, double* unit, int64_t* bad_idx, fem_stream_t stream);
+int fem_shell_geom(const double* coords, const int64_t* conn, int64_t M, int npe, const double* pt, double* unit,
+                   double* local, double* J, double* grads, double* B, int64_t* bad_idx, fem_stream_t stream);
+int fem_shell_apply(const double* Ke, const double* unit, const int64_t* conn, int npe, const int32_t* inc_ptr,
+                    const int32_t* inc, int64_t N, const double* u, double* y, fem_stream_t stream);
+int fem_shell_stress(const double* coords, const int64_t* conn, int64_t M, int npe, const double* D6,
+                     const double* pts, const double* u, double* nmq, int64_t* bad_idx, fem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
