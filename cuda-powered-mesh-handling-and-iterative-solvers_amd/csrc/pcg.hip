@@ -1972,6 +1972,34 @@ struct fem_pcg {
 // columns of the paired matrix copy: bs = 1 pairs its columns, bs = 3 (layout A) keeps cols16
 static const int16_t* pcols(const fem_pcg* s) { return s->bs == 1 ? s->pcols16 : s->cols16; }
 
+// ---------------------------------------------------------------- runtime format -> template arguments
+// The one place where a context's block size, column type and paired copy become template arguments: f is a generic
+// lambda; B() is the block size, typename decltype(ci)::type the column type, PAIR() the lane- / plane-paired copy.
+// A combination a kernel is not built for is kept out with `if constexpr` inside f (every branch here instantiates f).
+template <class CI>
+struct col_type {
+    using type = CI;
+};
+
+template <class F>
+static auto with_bs(int bs, F&& f) {
+    return bs == 3 ? f(std::integral_constant<int, 3>{}) : f(std::integral_constant<int, 1>{});
+}
+
+// f(B, ci, PAIR, cols, vals): the paired copy (when `paired`), else the 16-bit deltas, else the 32-bit columns
+template <class F>
+static auto with_matrix(const fem_pcg* s, bool paired, F&& f) {
+    return with_bs(s->bs, [&](auto B) {
+        if (paired) return f(B, col_type<int16_t>{}, std::true_type{}, pcols(s), (const double*)s->pvals);
+        if (s->cols16) return f(B, col_type<int16_t>{}, std::false_type{}, s->cols16, s->vals);
+        return f(B, col_type<int32_t>{}, std::false_type{}, s->cols, s->vals);
+    });
+}
+template <class F>
+static auto with_matrix(const fem_pcg* s, F&& f) {
+    return with_matrix(s, s->paired != 0, f);
+}
+
 static double* st_red(fem_pcg* s, int k) {
     return reinterpret_cast<double*>(reinterpret_cast<char*>(s->st) + offsetof(PcgState, red)) + k;
 }
@@ -2169,65 +2197,38 @@ __global__ void __launch_bounds__(PCG_BLOCK) k_cg1_mf_gather(MfOp op, const doub
 static int launch_mf_dot(fem_pcg* s) {
     const MfOp op = mf_op(s->mf);
     double* sl = s->mf_sl;
-    const int G = mf_resident_grid(s->bs == 3 ? (const void*)k_pcg_mf_dot<3> : (const void*)k_pcg_mf_dot<1>, MF_BLOCK,
-                                   op.nchunks);
-    if (s->bs == 3) hipLaunchKernelGGL(k_pcg_mf_dot<3>, dim3(G), dim3(MF_BLOCK), 0, s->stream, op, s->p0, sl, s->st, s->red);
-    else hipLaunchKernelGGL(k_pcg_mf_dot<1>, dim3(G), dim3(MF_BLOCK), 0, s->stream, op, s->p0, sl, s->st, s->red);
+    with_bs(s->bs, [&](auto B) {
+        const int G = mf_resident_grid((const void*)k_pcg_mf_dot<B()>, MF_BLOCK, op.nchunks);
+        hipLaunchKernelGGL(k_pcg_mf_dot<B()>, dim3(G), dim3(MF_BLOCK), 0, s->stream, op, s->p0, sl, s->st, s->red);
+    });
     FEM_LAUNCHED();
     s->mf_qfuse = s->upd1 && !(s->tune & FEM_TUNE_MF_GATHER);
     if (op.nnodes > 0 && !s->mf_qfuse) {
-        if (s->bs == 3) hipLaunchKernelGGL(k_mf_gather<3>, dim3(stream_grid(op.nnodes, 256)), dim3(256), 0, s->stream, op, sl, s->q);
-        else hipLaunchKernelGGL(k_mf_gather<1>, dim3(stream_grid(op.nnodes, 256)), dim3(256), 0, s->stream, op, sl, s->q);
+        with_bs(s->bs, [&](auto B) {
+            hipLaunchKernelGGL(k_mf_gather<B()>, dim3(stream_grid(op.nnodes, 256)), dim3(256), 0, s->stream, op, sl,
+                               s->q);
+        });
         FEM_LAUNCHED();
     }
     return FEM_OK;
 }
 
+// K1 of the 3-kernel / fused schedules. The paired copy (sell_pair.hpp / sell_pair3.hpp) is read by the unfused form
+// only; the distributed path never fuses.
 static int launch_spmv_dot(fem_pcg* s) {
     if (s->mf) return launch_mf_dot(s);
-    if (s->cols16) {
-#define FEM_K1D(B, F, D)                                                                                           \
-    hipLaunchKernelGGL((k_pcg_spmv_dot<B, F, D, int16_t>), dim3(s->grid_spmv), dim3(PCG_BLOCK), 0, s->stream,     \
-                       s->nslices, s->nrows, s->slice_ptr, s->cols16, s->vals, s->p0, s->p1, s->r, s->w, s->x, s->q, \
-                       s->st, s->red, s->tune & FEM_TUNE_REVERSE)
-        if (s->paired && !s->fused) {   // 16-byte-value copy of the matrix (sell_pair.hpp / sell_pair3.hpp)
-            if (s->bs == 1)
-                hipLaunchKernelGGL((k_pcg_spmv_dot<1, false, true, int16_t, true>), dim3(s->grid_spmv), dim3(PCG_BLOCK),
-                                   0, s->stream, s->nslices, s->nrows, s->slice_ptr, pcols(s), s->pvals, s->p0, s->p1,
-                                   s->r, s->w, s->x, s->q, s->st, s->red, s->tune & FEM_TUNE_REVERSE);
-            else
-                hipLaunchKernelGGL((k_pcg_spmv_dot<3, false, true, int16_t, true>), dim3(s->grid_spmv), dim3(PCG_BLOCK),
-                                   0, s->stream, s->nslices, s->nrows, s->slice_ptr, pcols(s), s->pvals, s->p0, s->p1,
-                                   s->r, s->w, s->x, s->q, s->st, s->red, s->tune & FEM_TUNE_REVERSE);
-        } else if (s->dist) {
-            if (s->bs == 1) FEM_K1D(1, false, true);
-            else FEM_K1D(3, false, true);
-        } else if (s->bs == 1) {
-            if (s->fused) FEM_K1D(1, true, true);
-            else FEM_K1D(1, false, true);
-        } else {
-            if (s->fused) FEM_K1D(3, true, true);
-            else FEM_K1D(3, false, true);
-        }
-#undef FEM_K1D
-        FEM_LAUNCHED();
-        return FEM_OK;
-    }
-#define FEM_K1(B, F, D)                                                                                            \
-    hipLaunchKernelGGL((k_pcg_spmv_dot<B, F, D>), dim3(s->grid_spmv), dim3(PCG_BLOCK), 0, s->stream, s->nslices,   \
-                       s->nrows, s->slice_ptr, s->cols, s->vals, s->p0, s->p1, s->r, s->w, s->x, s->q, s->st, s->red,  \
-                       s->tune & FEM_TUNE_REVERSE)
-    if (s->dist) {
-        if (s->bs == 1) FEM_K1(1, false, true);
-        else FEM_K1(3, false, true);
-    } else if (s->bs == 1) {
-        if (s->fused) FEM_K1(1, true, true);
-        else FEM_K1(1, false, true);
-    } else {
-        if (s->fused) FEM_K1(3, true, true);
-        else FEM_K1(3, false, true);
-    }
-#undef FEM_K1
+    const bool fused = s->fused && !s->dist;
+    with_matrix(s, s->cols16 && s->paired && !s->fused, [&](auto B, auto ci, auto PAIR, auto* cols, const double* vals) {
+        using CI = typename decltype(ci)::type;
+        auto launch = [&](auto FUSED) {
+            if constexpr (!(FUSED() && PAIR()))   // no fused build over the paired copy
+                hipLaunchKernelGGL((k_pcg_spmv_dot<B(), FUSED(), true, CI, PAIR()>), dim3(s->grid_spmv),
+                                   dim3(PCG_BLOCK), 0, s->stream, s->nslices, s->nrows, s->slice_ptr, cols, vals, s->p0,
+                                   s->p1, s->r, s->w, s->x, s->q, s->st, s->red, s->tune & FEM_TUNE_REVERSE);
+        };
+        if (fused) launch(std::true_type{});
+        else launch(std::false_type{});
+    });
     FEM_LAUNCHED();
     return FEM_OK;
 }
@@ -2269,111 +2270,88 @@ static P2PArgs p2p_args(const fem_pcg* s) {
     return x;
 }
 
+// the tail of every single-reduction launch: the group path without neighbour exchange sums recv in place, so it gets
+// this rank's send buffer (with p2p the caller moves psend -> the peers' precv; RCCL reduces send -> recv itself)
+static int cg1_group_copy(fem_pcg* s) {
+    if (!s->comm && !s->p2p)
+        FEM_HIP(hipMemcpyAsync(s->cg1_recv, s->cg1_send, sizeof(double) * (size_t)cg1_len(s), hipMemcpyDeviceToDevice,
+                               s->stream));
+    return FEM_OK;
+}
+
 static int cg1_spmv(fem_pcg* s, int always) {
     const int64_t off = s->nI * s->bs;
     const int32_t* ipos = s->nI > 0 ? s->ipos : nullptr;
+    const P2PArgs xp = p2p_args(s);
     if (s->mf && s->mf_nogather) {   // chunks into the slots + d, then the interface pack only
         const MfOp op = mf_op(s->mf);
-        const P2PArgs xp = p2p_args(s);
         if (op.nchunks > 0) {
-            const void* fn = s->bs == 3 ? (const void*)k_cg1_mf_slots_dot<3> : (const void*)k_cg1_mf_slots_dot<1>;
-            const int G = mf_resident_grid(fn, MF_BLOCK, op.nchunks);
-            if (s->bs == 3)
-                hipLaunchKernelGGL(k_cg1_mf_slots_dot<3>, dim3(G), dim3(MF_BLOCK), 0, s->stream, op, s->cg1_u,
+            with_bs(s->bs, [&](auto B) {
+                const int G = mf_resident_grid((const void*)k_cg1_mf_slots_dot<B()>, MF_BLOCK, op.nchunks);
+                hipLaunchKernelGGL(k_cg1_mf_slots_dot<B()>, dim3(G), dim3(MF_BLOCK), 0, s->stream, op, s->cg1_u,
                                    s->mf_sl, s->st, always, xp, s->cg1_recv, s->cg1_send, off, s->red);
-            else
-                hipLaunchKernelGGL(k_cg1_mf_slots_dot<1>, dim3(G), dim3(MF_BLOCK), 0, s->stream, op, s->cg1_u,
-                                   s->mf_sl, s->st, always, xp, s->cg1_recv, s->cg1_send, off, s->red);
+            });
             FEM_LAUNCHED();
         } else {   // no element on this rank: d = 0
             FEM_HIP(hipMemsetAsync(st_red(s, 0), 0, sizeof(double), s->stream));
         }
         const int Gi = grid_multiple_of_xcd(cdiv(s->nI > 0 ? s->nI : 1, PCG_BLOCK), 1024);
         const int32_t* imap = s->nI > 0 ? s->imap : nullptr;
-        if (s->bs == 3)
-            hipLaunchKernelGGL(k_cg1_mf_iface<3>, dim3(Gi), dim3(PCG_BLOCK), 0, s->stream, op, s->mf_sl, imap, s->nI,
+        with_bs(s->bs, [&](auto B) {
+            hipLaunchKernelGGL(k_cg1_mf_iface<B()>, dim3(Gi), dim3(PCG_BLOCK), 0, s->stream, op, s->mf_sl, imap, s->nI,
                                s->cg1_send, off, s->st, s->red, always, xp, s->cg1_recv, s->hist, s->hist_len);
-        else
-            hipLaunchKernelGGL(k_cg1_mf_iface<1>, dim3(Gi), dim3(PCG_BLOCK), 0, s->stream, op, s->mf_sl, imap, s->nI,
-                               s->cg1_send, off, s->st, s->red, always, xp, s->cg1_recv, s->hist, s->hist_len);
-        FEM_LAUNCHED();
-        if (!s->comm && s->p2p) return FEM_OK;
-        if (!s->comm)
-            FEM_HIP(hipMemcpyAsync(s->cg1_recv, s->cg1_send, sizeof(double) * (size_t)cg1_len(s),
-                                   hipMemcpyDeviceToDevice, s->stream));
-        return FEM_OK;
-    }
-    if (s->mf) {   // element-chunk operator: the rank's chunks into the context's slots, then the slot gather
+        });
+    } else if (s->mf) {   // element-chunk operator: the rank's chunks into the context's slots, then the slot gather
         const MfOp op = mf_op(s->mf);
-        const P2PArgs xp = p2p_args(s);
         if (op.nchunks > 0) {
-            const void* fn = s->bs == 3 ? (const void*)k_cg1_mf_slots<3> : (const void*)k_cg1_mf_slots<1>;
-            const int G = mf_resident_grid(fn, MF_BLOCK, op.nchunks);
-            if (s->bs == 3)
-                hipLaunchKernelGGL(k_cg1_mf_slots<3>, dim3(G), dim3(MF_BLOCK), 0, s->stream, op, s->cg1_u, s->mf_sl,
+            with_bs(s->bs, [&](auto B) {
+                const int G = mf_resident_grid((const void*)k_cg1_mf_slots<B()>, MF_BLOCK, op.nchunks);
+                hipLaunchKernelGGL(k_cg1_mf_slots<B()>, dim3(G), dim3(MF_BLOCK), 0, s->stream, op, s->cg1_u, s->mf_sl,
                                    s->st, always, xp, s->cg1_recv, s->cg1_send, off);
-            else
-                hipLaunchKernelGGL(k_cg1_mf_slots<1>, dim3(G), dim3(MF_BLOCK), 0, s->stream, op, s->cg1_u, s->mf_sl,
-                                   s->st, always, xp, s->cg1_recv, s->cg1_send, off);
+            });
             FEM_LAUNCHED();
         }
         const int Gg = grid_multiple_of_xcd(cdiv(s->nrows, PCG_BLOCK), 1024);
-        if (s->bs == 3)
-            hipLaunchKernelGGL(k_cg1_mf_gather<3>, dim3(Gg), dim3(PCG_BLOCK), 0, s->stream, op, s->mf_sl, s->cg1_u,
+        with_bs(s->bs, [&](auto B) {
+            hipLaunchKernelGGL(k_cg1_mf_gather<B()>, dim3(Gg), dim3(PCG_BLOCK), 0, s->stream, op, s->mf_sl, s->cg1_u,
                                s->q, ipos, s->cg1_send, off, s->st, s->red, always, xp, s->cg1_recv, s->hist,
                                s->hist_len);
-        else
-            hipLaunchKernelGGL(k_cg1_mf_gather<1>, dim3(Gg), dim3(PCG_BLOCK), 0, s->stream, op, s->mf_sl, s->cg1_u,
-                               s->q, ipos, s->cg1_send, off, s->st, s->red, always, xp, s->cg1_recv, s->hist,
-                               s->hist_len);
-        FEM_LAUNCHED();
-        if (!s->comm && s->p2p) return FEM_OK;
-        if (!s->comm)
-            FEM_HIP(hipMemcpyAsync(s->cg1_recv, s->cg1_send, sizeof(double) * (size_t)cg1_len(s),
-                                   hipMemcpyDeviceToDevice, s->stream));
-        return FEM_OK;
+        });
+    } else {
+        with_matrix(s, [&](auto B, auto ci, auto PAIR, auto* cols, const double* vals) {
+            hipLaunchKernelGGL((k_cg1_spmv<B(), typename decltype(ci)::type, PAIR()>), dim3(s->grid_spmv),
+                               dim3(PCG_BLOCK), 0, s->stream, s->nslices, s->nrows, s->slice_ptr, cols, vals, s->cg1_u,
+                               s->q, ipos, s->cg1_send, off, s->st, s->red, always, s->tune & FEM_TUNE_REVERSE, xp,
+                               s->cg1_recv, s->hist, s->hist_len);
+        });
     }
-#define FEM_CG1(B, CI, PR, C, V)                                                                                   \
-    hipLaunchKernelGGL((k_cg1_spmv<B, CI, PR>), dim3(s->grid_spmv), dim3(PCG_BLOCK), 0, s->stream, s->nslices,     \
-                       s->nrows, s->slice_ptr, C, V, s->cg1_u, s->q, ipos, s->cg1_send, off, s->st, s->red, always, \
-                       s->tune & FEM_TUNE_REVERSE, p2p_args(s), s->cg1_recv, s->hist, s->hist_len)
-    if (s->paired && s->bs == 1) FEM_CG1(1, int16_t, true, pcols(s), s->pvals);
-    else if (s->paired) FEM_CG1(3, int16_t, true, pcols(s), s->pvals);
-    else if (s->cols16 && s->bs == 1) FEM_CG1(1, int16_t, false, s->cols16, s->vals);
-    else if (s->cols16) FEM_CG1(3, int16_t, false, s->cols16, s->vals);
-    else if (s->bs == 1) FEM_CG1(1, int32_t, false, s->cols, s->vals);
-    else FEM_CG1(3, int32_t, false, s->cols, s->vals);
-#undef FEM_CG1
     FEM_LAUNCHED();
-    if (!s->comm && s->p2p) return FEM_OK;   // group path: the caller moves psend -> peers' precv
-    if (!s->comm)
-        FEM_HIP(hipMemcpyAsync(s->cg1_recv, s->cg1_send, sizeof(double) * (size_t)cg1_len(s), hipMemcpyDeviceToDevice,
-                               s->stream));
-    return FEM_OK;
+    return cg1_group_copy(s);
 }
 
 static int cg1_step_update(fem_pcg* s) {
-    if (s->mf && s->mf_nogather)
-        hipLaunchKernelGGL(k_cg1_update<true>, dim3(s->grid_vec), dim3(PCG_BLOCK), 0, s->stream, s->n, s->bs, s->x,
+    const bool mf = s->mf && s->mf_nogather;   // v summed from the operator's slots inside the update
+    const MfOp op = mf ? mf_op(s->mf) : MfOp{};
+    auto launch = [&](auto MF) {
+        hipLaunchKernelGGL(k_cg1_update<MF()>, dim3(s->grid_vec), dim3(PCG_BLOCK), 0, s->stream, s->n, s->bs, s->x,
                            s->r, s->p0, s->cg1_s, s->cg1_u, s->q, s->w, s->cg1_recv, s->nI > 0 ? s->ipos : nullptr,
-                           s->own, s->st, s->red, p2p_args(s), s->cg1_send, s->nI * s->bs, mf_op(s->mf), s->mf_sl);
-    else
-        hipLaunchKernelGGL(k_cg1_update<false>, dim3(s->grid_vec), dim3(PCG_BLOCK), 0, s->stream, s->n, s->bs, s->x,
-                           s->r, s->p0, s->cg1_s, s->cg1_u, s->q, s->w, s->cg1_recv, s->nI > 0 ? s->ipos : nullptr,
-                           s->own, s->st, s->red, p2p_args(s), s->cg1_send, s->nI * s->bs);
+                           s->own, s->st, s->red, p2p_args(s), s->cg1_send, s->nI * s->bs, op,
+                           mf ? (const double*)s->mf_sl : nullptr);
+    };
+    if (mf) launch(std::true_type{});
+    else launch(std::false_type{});
     FEM_LAUNCHED();
     return FEM_OK;
 }
 
 // fused iteration setup (at fem_pcg_start of a single-reduction distributed context with FEM_TUNE_C1F): the grid
 // (resident by the occupancy query), the gather windows of this matrix, zeroed flags
-static const void* c1f_fn(const fem_pcg* s) {
-    if (s->paired && s->bs == 1) return (const void*)k_cg1_fused<1, int16_t, true>;
-    if (s->paired) return (const void*)k_cg1_fused<3, int16_t, true>;
-    if (s->cols16 && s->bs == 1) return (const void*)k_cg1_fused<1, int16_t, false>;
-    if (s->cols16) return (const void*)k_cg1_fused<3, int16_t, false>;
-    if (s->bs == 1) return (const void*)k_cg1_fused<1, int32_t, false>;
-    return (const void*)k_cg1_fused<3, int32_t, false>;
+// the build of k_cg1_fused for this context's matrix; `a` (launches) gets the matching columns and values
+static const void* c1f_fn(const fem_pcg* s, Cg1FArgs* a = nullptr) {
+    return with_matrix(s, [&](auto B, auto ci, auto PAIR, auto* cols, const double* vals) {
+        if (a) a->cols = cols, a->vals = vals;
+        return (const void*)k_cg1_fused<B(), typename decltype(ci)::type, PAIR()>;
+    });
 }
 
 // Context buffers of bs = 1 solves (vectors, reduction words, the paired matrix copy, persistent-kernel words) are
@@ -2543,10 +2521,13 @@ static int u2_setup(fem_pcg* s) {
         FEM_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
         // the element-chunk forms: the smaller residency of the two (slot sums / q read) per block size
         int nb2 = 0;
-        const void* fn = var == 0 ? (const void*)k_pcg_update2 : var == 1 ? (const void*)k_pcg_update2_mf<1, false>
-                                                                       : (const void*)k_pcg_update2_mf<3, false>;
-        const void* fn2 = var == 0 ? fn : var == 1 ? (const void*)k_pcg_update2_mf<1, true>
-                                                   : (const void*)k_pcg_update2_mf<3, true>;
+        const void* fn = (const void*)k_pcg_update2;
+        const void* fn2 = fn;
+        if (s->mf)
+            with_bs(s->bs, [&](auto B) {
+                fn = (const void*)k_pcg_update2_mf<B(), false>;
+                fn2 = (const void*)k_pcg_update2_mf<B(), true>;
+            });
         FEM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb2, fn2, PCG_BLOCK, 0));
         FEM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, PCG_BLOCK, 0));
         nb = nb2 < nb ? nb2 : nb;
@@ -2576,17 +2557,15 @@ static int launch_update2(fem_pcg* s) {
         const MfOp op = mf_op(s->mf);
         const double* sl = s->mf_sl;
         const int64_t nn = s->nrows;
-#define FEM_U2MF(B, FQ)                                                                                               \
-    hipLaunchKernelGGL((k_pcg_update2_mf<B, FQ>), dim3(s->u2_grid), dim3(PCG_BLOCK), 0, s->stream, nn, s->x, s->p0,    \
-                       s->r, s->q, s->w, s->st, s->red, s->hist, s->hist_len, s->u2_sync, hold, op, sl)
-        if (s->bs == 3) {
-            if (s->mf_qfuse) FEM_U2MF(3, false);
-            else FEM_U2MF(3, true);
-        } else {
-            if (s->mf_qfuse) FEM_U2MF(1, false);
-            else FEM_U2MF(1, true);
-        }
-#undef FEM_U2MF
+        with_bs(s->bs, [&](auto B) {
+            auto launch = [&](auto FROM_Q) {
+                hipLaunchKernelGGL((k_pcg_update2_mf<B(), FROM_Q()>), dim3(s->u2_grid), dim3(PCG_BLOCK), 0, s->stream,
+                                   nn, s->x, s->p0, s->r, s->q, s->w, s->st, s->red, s->hist, s->hist_len, s->u2_sync,
+                                   hold, op, sl);
+            };
+            if (s->mf_qfuse) launch(std::false_type{});
+            else launch(std::true_type{});
+        });
         FEM_LAUNCHED();
         return FEM_OK;
     }
@@ -2601,16 +2580,7 @@ static int c1f_launch(fem_pcg* s) {
     a.nslices = s->nslices;
     a.nrows = s->nrows;
     a.slice_ptr = s->slice_ptr;
-    if (s->paired) {
-        a.cols = pcols(s);
-        a.vals = s->pvals;
-    } else if (s->cols16) {
-        a.cols = s->cols16;
-        a.vals = s->vals;
-    } else {
-        a.cols = s->cols;
-        a.vals = s->vals;
-    }
+    const void* fn = c1f_fn(s, &a);   // (a.cols, a.vals)
     a.x = s->x;
     a.r = s->r;
     a.p = s->p0;
@@ -2632,12 +2602,20 @@ static int c1f_launch(fem_pcg* s) {
     a.flags = s->c1f_flags;
     a.tune_rev = (s->tune & FEM_TUNE_REVERSE) ? 1 : 0;
     void* args[] = {&a};
-    FEM_HIP(hipLaunchKernel(c1f_fn(s), dim3(s->c1f_grid), dim3(C1F_BLOCK), args, 0, s->stream));
+    FEM_HIP(hipLaunchKernel(fn, dim3(s->c1f_grid), dim3(C1F_BLOCK), args, 0, s->stream));
     FEM_LAUNCHED();
-    if (!s->comm && !s->p2p)   // group path: the caller sums recv in place
-        FEM_HIP(hipMemcpyAsync(s->cg1_recv, s->cg1_send, sizeof(double) * (size_t)cg1_len(s), hipMemcpyDeviceToDevice,
-                               s->stream));
-    return FEM_OK;
+    return cg1_group_copy(s);
+}
+
+// q = A x0 at the start of a solve: the element formula, the caller's solver layout (`layout`: the single-GPU start
+// reads the paired values), else the plain arrays
+static int start_spmv(fem_pcg* s, bool layout) {
+    const fem_stream_t st = reinterpret_cast<fem_stream_t>(s->stream);
+    if (s->mf) return mf_apply(s->mf, s->x, s->q, s->mf_sl, s->stream);
+    if (layout && s->pext)
+        return fem_spmv_sl(s->nrows, s->bs, s->slice_ptr, pcols(s), s->pvals, s->puoff, s->pucol, s->x, s->q, st);
+    return s->cols16 ? fem_spmv16(s->nrows, s->bs, s->slice_ptr, s->cols16, s->vals, s->x, s->q, st)
+                     : fem_spmv(s->nrows, s->bs, s->slice_ptr, s->cols, s->vals, s->x, s->q, st);
 }
 
 static int dist_phase(fem_pcg* s, int phase) {
@@ -2667,14 +2645,7 @@ static int dist_phase(fem_pcg* s, int phase) {
                                    s->w);
                 FEM_LAUNCHED();
             }
-            if (s->mf) {
-                if ((rc = mf_apply(s->mf, s->x, s->q, s->mf_sl, s->stream))) return rc;
-            } else if ((rc = (s->cols16 ? fem_spmv16(s->nrows, s->bs, s->slice_ptr, s->cols16, s->vals, s->x, s->q,
-                                                     s->stream)
-                                        : fem_spmv(s->nrows, s->bs, s->slice_ptr, s->cols, s->vals, s->x, s->q,
-                                                   s->stream)))) {
-                return rc;
-            }
+            if ((rc = start_spmv(s, false))) return rc;
             return halo_pack(s, s->q, false, false);
         case 11:
             hipLaunchKernelGGL(k_halo_unpack<false>, dim3(s->grid_vec), dim3(PCG_BLOCK), 0, s->stream, s->nrows, s->bs,
@@ -2828,27 +2799,11 @@ static int launch_deferred(fem_pcg* s, int which) {
     const int par = (int)(s->launched & 1);
     const int rev = (s->tune & FEM_TUNE_REVERSE) ? par : 0;
     if (which == 0) {
-        if (s->paired && s->bs == 1) {
-            hipLaunchKernelGGL((k_pcg_d1<1, int16_t, true>), dim3(s->grid_spmv), dim3(PCG_BLOCK), 0, s->stream,
-                               s->nslices, s->nrows, s->slice_ptr, pcols(s), s->pvals, s->p0, s->q, s->st, par, rev,
-                               s->red.partials);
-        } else if (s->paired) {
-            hipLaunchKernelGGL((k_pcg_d1<3, int16_t, true>), dim3(s->grid_spmv), dim3(PCG_BLOCK), 0, s->stream,
-                               s->nslices, s->nrows, s->slice_ptr, pcols(s), s->pvals, s->p0, s->q, s->st, par, rev,
-                               s->red.partials);
-        } else if (s->cols16) {
-            if (s->bs == 1)
-                hipLaunchKernelGGL((k_pcg_d1<1, int16_t>), dim3(s->grid_spmv), dim3(PCG_BLOCK), 0, s->stream, s->nslices,
-                                   s->nrows, s->slice_ptr, s->cols16, s->vals, s->p0, s->q, s->st, par, rev, s->red.partials);
-            else
-                hipLaunchKernelGGL((k_pcg_d1<3, int16_t>), dim3(s->grid_spmv), dim3(PCG_BLOCK), 0, s->stream, s->nslices,
-                                   s->nrows, s->slice_ptr, s->cols16, s->vals, s->p0, s->q, s->st, par, rev, s->red.partials);
-        } else if (s->bs == 1)
-            hipLaunchKernelGGL(k_pcg_d1<1>, dim3(s->grid_spmv), dim3(PCG_BLOCK), 0, s->stream, s->nslices, s->nrows,
-                               s->slice_ptr, s->cols, s->vals, s->p0, s->q, s->st, par, rev, s->red.partials);
-        else
-            hipLaunchKernelGGL(k_pcg_d1<3>, dim3(s->grid_spmv), dim3(PCG_BLOCK), 0, s->stream, s->nslices, s->nrows,
-                               s->slice_ptr, s->cols, s->vals, s->p0, s->q, s->st, par, rev, s->red.partials);
+        with_matrix(s, [&](auto B, auto ci, auto PAIR, auto* cols, const double* vals) {
+            hipLaunchKernelGGL((k_pcg_d1<B(), typename decltype(ci)::type, PAIR()>), dim3(s->grid_spmv),
+                               dim3(PCG_BLOCK), 0, s->stream, s->nslices, s->nrows, s->slice_ptr, cols, vals, s->p0, s->q,
+                               s->st, par, rev, s->red.partials);
+        });
     } else if (which == 1) {
         hipLaunchKernelGGL(k_pcg_d2, dim3(s->grid_vec), dim3(PCG_BLOCK), 0, s->stream, s->n, s->r, s->q, s->w, s->st,
                            par, s->red.partials, s->grid_spmv, s->red.partials + MAX_PARTIALS);
@@ -2858,6 +2813,159 @@ static int launch_deferred(fem_pcg* s, int which) {
         s->launched++;
     }
     FEM_LAUNCHED();
+    return FEM_OK;
+}
+
+// ---------------------------------------------------------------- the persistent builds
+// Every compiled persistent kernel is one row of PK_BUILDS, and only a row's function pointer is ever launched. The
+// residency checks walk the rows of a family, persist_plan picks the row of a context. A new build is one more row
+// here plus, where the choice between rows changes, one more line in persist_plan.
+enum PkFamily { PKF_BS1, PKF_BS1_DIST, PKF_BS3, PKF_GV };   // k_pcg_persist (single GPU, DIST), _persist3, _persist_gv
+
+struct PkBuild {
+    PkFamily fam;
+    int slots;   // register slots per wave
+    bool prof;   // phase clocks (fem_pcg_persist_profile, fem_pcg_set_prof)
+    bool gsc1;   // sc1 u gathers (FEM_TUNE_PK_SC1)
+    bool ovf;    // rows past the register slots streamed from HBM
+    bool dist;   // rows partitioned over ranks (fem_pcg_set_rows)
+    bool od;     // diagonal-free value stream (FEM_TUNE_PK_OFFDIAG)
+    const void* fn;
+    size_t lds;  // dynamic LDS bytes of a launch
+};
+
+// a row's key and its template arguments come from the same parameters
+template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false, bool OD = false>
+static PkBuild pk1_build() {
+    return {DIST ? PKF_BS1_DIST : PKF_BS1, MAXS, PROF, GSC1, OVF, DIST, OD,
+            (const void*)k_pcg_persist<MAXS, PROF, GSC1, OVF, DIST, OD>, PK_LDS};
+}
+template <bool OVF, bool DIST>
+static PkBuild pk3_build() {
+    return {PKF_BS3, P3_MAXS, false, true, OVF, DIST, false, (const void*)k_pcg_persist3<P3_MAXS, OVF, DIST>, P3_LDS};
+}
+template <int MAXS, bool DIST>
+static PkBuild gv_build() {
+    return {PKF_GV, MAXS, false, true, false, DIST, false, (const void*)k_pcg_persist_gv<MAXS, DIST>, GV_LDS};
+}
+
+// distributed builds: 4 register slots per wave when the rank's slices fit (every rank of a 10M-tet system at
+// N >= 2: fewer loop-carried registers, no spills), else 7
+constexpr int PK_MAXS_DIST = 4;
+
+static const PkBuild PK_BUILDS[] = {
+    // bs = 1, single GPU: 1, 2 and 4 slots for 1, 2 and 3-4 packed slices per wave (8, 4, 4 lane pairs in flight),
+    // else 7 slots (2 in flight) with plain or sc1 gathers, instrumented, overflow
+    pk1_build<1, false, true>(),
+    pk1_build<2, false, true>(),
+    pk1_build<4, false, true>(),
+    pk1_build<PK_MAXS, false, true>(),
+    pk1_build<PK_MAXS, false, false>(),
+    pk1_build<PK_MAXS, true, true>(),
+    pk1_build<PK_MAXS, true, false>(),
+    pk1_build<PK_MAXS, false, true, true>(),
+    pk1_build<PK_MAXS, false, false, true>(),
+    // the same nine over the diagonal-free value stream
+    pk1_build<1, false, true, false, false, true>(),
+    pk1_build<2, false, true, false, false, true>(),
+    pk1_build<4, false, true, false, false, true>(),
+    pk1_build<PK_MAXS, false, true, false, false, true>(),
+    pk1_build<PK_MAXS, false, false, false, false, true>(),
+    pk1_build<PK_MAXS, true, true, false, false, true>(),
+    pk1_build<PK_MAXS, true, false, false, false, true>(),
+    pk1_build<PK_MAXS, false, true, true, false, true>(),
+    pk1_build<PK_MAXS, false, false, true, false, true>(),
+    // bs = 1, DIST: always sc1 gathers, never overflow; instrumented forms of the two larger ones only
+    pk1_build<1, false, true, false, true>(),
+    pk1_build<2, false, true, false, true>(),
+    pk1_build<PK_MAXS_DIST, false, true, false, true>(),
+    pk1_build<PK_MAXS_DIST, true, true, false, true>(),
+    pk1_build<PK_MAXS, false, true, false, true>(),
+    pk1_build<PK_MAXS, true, true, false, true>(),
+    // bs = 3 (pcg_persist3.hpp): P3_MAXS slices per wave on chip, the overflow build past that (single GPU), DIST
+    pk3_build<false, false>(),
+    pk3_build<true, false>(),
+    pk3_build<false, true>(),
+    // pipelined bs = 1 (pcg_persist_gv.hpp): one or two packed slices per wave, single GPU and DIST
+    gv_build<1, false>(),
+    gv_build<2, false>(),
+    gv_build<1, true>(),
+    gv_build<2, true>(),
+};
+
+static const PkBuild* pk_find(PkFamily fam, int slots, bool prof, bool gsc1, bool ovf, bool dist, bool od) {
+    for (const PkBuild& b : PK_BUILDS)
+        if (b.fam == fam && b.slots == slots && b.prof == prof && b.gsc1 == gsc1 && b.ovf == ovf && b.dist == dist &&
+            b.od == od)
+            return &b;
+    return nullptr;
+}
+
+// on-chip capacity of a family: the slots of its largest build
+static int pk_max_slots(PkFamily fam) {
+    int m = 0;
+    for (const PkBuild& b : PK_BUILDS)
+        if (b.fam == fam && b.slots > m) m = b.slots;
+    return m;
+}
+
+// packed slice assignment: slices per wave = ceil(max slices of a workgroup / waves)
+static int pk_pack(int64_t nslices, int G) {
+    const int64_t maxL = (nslices + G - 1) / G;
+    return (int)((maxL + PK_WAVES - 1) / PK_WAVES);
+}
+
+// slices this context's launches own: the rank's share of a row-partitioned system, else all
+static int64_t pk_own_slices(const fem_pcg* s) {
+    return s->pd ? s->pd_split[s->pd_rank + 1] - s->pd_split[s->pd_rank] : s->nslices;
+}
+
+// The build a started context launches and the `pack` its kernel gets (PkArgs::pack; 0: the even spread, single-GPU
+// bs = 1 without FEM_TUNE_PK_PACK only). prof: the instrumented form where one exists (none for overflow). gv: the
+// pipelined kernel; false gives the single-reduction build of the same context (what fem_pcg_persist_build reports).
+struct PkPlan {
+    const PkBuild* b;   // nullptr: no such build (never for a context that persist_setup accepted)
+    int pack;
+};
+
+static PkPlan persist_plan(const fem_pcg* s, bool prof, bool gv) {
+    const int pk = pk_pack(pk_own_slices(s), s->pk_grid);
+    const bool dist = s->pd != 0;
+    if (gv) return {pk_find(PKF_GV, pk <= 1 ? 1 : 2, false, true, false, dist, false), pk};
+    if (s->bs == 3) return {pk_find(PKF_BS3, P3_MAXS, false, true, !dist && s->pk_ovf, dist, false), pk};
+    if (dist) {   // 1, 2, PK_MAXS_DIST, PK_MAXS slots from the rank's pack; instrumented: the last two only
+        const int slots = !prof && pk <= 1 ? 1 : !prof && pk == 2 ? 2 : pk <= PK_MAXS_DIST ? PK_MAXS_DIST : PK_MAXS;
+        return {pk_find(PKF_BS1_DIST, slots, prof, true, false, true, false), pk};
+    }
+    const int pack = (s->tune & FEM_TUNE_PK_PACK) ? pk : 0;
+    const bool ovf = s->pk_ovf != 0, gsc1 = (s->tune & FEM_TUNE_PK_SC1) != 0;
+    prof = prof && !ovf;
+    const bool small = pack >= 1 && pack <= 4 && !(s->tune & FEM_TUNE_PK_WIDE) && !prof && !ovf && gsc1;
+    const int slots = !small ? PK_MAXS : pack == 1 ? 1 : pack == 2 ? 2 : 4;
+    return {pk_find(PKF_BS1, slots, prof, gsc1, ovf, false, s->pk_od != 0), pack};
+}
+static PkPlan persist_plan(const fem_pcg* s, bool prof) { return persist_plan(s, prof, s->pk_gv && s->bs == 1); }
+
+// LDS attribute and occupancy of one build: *nb workgroups of `threads` resident per CU
+static int check_resident(const void* fn, int threads, size_t lds, int* nb) {
+    FEM_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    FEM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(nb, fn, threads, lds));
+    return FEM_OK;
+}
+
+// every single-GPU or every DIST build of a family, each row once: *res = 1 all resident, 2 not
+static int family_resident(PkFamily fam, bool dist, int* res) {
+    *res = 1;
+    for (const PkBuild& b : PK_BUILDS) {
+        if (b.fam != fam || b.dist != dist) continue;
+        int nb = 0;
+        const int rc = check_resident(b.fn, PK_T, b.lds, &nb);
+        if (rc) return rc;
+        if (nb < 1) {
+            *res = 2;
+            break;
+        }
+    }
     return FEM_OK;
 }
 
@@ -2899,42 +3007,35 @@ static int launch_iterations(fem_pcg* s, int k) {
     return FEM_OK;
 }
 
-extern "C" {
-
-int fem_spmv(int64_t nrows, int bs, const int64_t* slice_ptr, const int32_t* cols, const double* vals, const double* x,
-             double* y, fem_stream_t stream) {
+// y = A x on the plain SELL arrays, 32-bit columns or 16-bit deltas (fem_spmv / fem_spmv16)
+template <class CI>
+static int spmv_plain(const char* fn, int64_t nrows, int bs, const int64_t* slice_ptr, const CI* cols,
+                      const double* vals, const double* x, double* y, fem_stream_t stream) {
     const int64_t ns = cdiv(nrows, 64);
     if (ns == 0) return FEM_OK;
-    const int grid = grid_multiple_of_xcd(cdiv(ns, 4), 2048);
-    if (bs == 1)
-        hipLaunchKernelGGL(k_spmv<1>, dim3(grid), dim3(256), 0, S(stream), ns, nrows, slice_ptr, cols, vals, x, y);
-    else if (bs == 3)
-        hipLaunchKernelGGL(k_spmv<3>, dim3(grid), dim3(256), 0, S(stream), ns, nrows, slice_ptr, cols, vals, x, y);
-    else {
-        set_error("fem_spmv: block size %d unsupported", bs);
+    if (bs != 1 && bs != 3) {
+        set_error("%s: block size %d unsupported", fn, bs);
         return FEM_EARG;
     }
+    const int grid = grid_multiple_of_xcd(cdiv(ns, 4), 2048);
+    with_bs(bs, [&](auto B) {
+        hipLaunchKernelGGL((k_spmv<B(), SPMV_U, false, CI>), dim3(grid), dim3(256), 0, S(stream), ns, nrows, slice_ptr,
+                           cols, vals, x, y);
+    });
     FEM_LAUNCHED();
     return FEM_OK;
 }
 
+extern "C" {
+
+int fem_spmv(int64_t nrows, int bs, const int64_t* slice_ptr, const int32_t* cols, const double* vals, const double* x,
+             double* y, fem_stream_t stream) {
+    return spmv_plain("fem_spmv", nrows, bs, slice_ptr, cols, vals, x, y, stream);
+}
+
 int fem_spmv16(int64_t nrows, int bs, const int64_t* slice_ptr, const int16_t* dcols, const double* vals,
                const double* x, double* y, fem_stream_t stream) {
-    const int64_t ns = cdiv(nrows, 64);
-    if (ns == 0) return FEM_OK;
-    const int grid = grid_multiple_of_xcd(cdiv(ns, 4), 2048);
-    if (bs == 1)
-        hipLaunchKernelGGL((k_spmv<1, SPMV_U, false, int16_t>), dim3(grid), dim3(256), 0, S(stream), ns, nrows,
-                           slice_ptr, dcols, vals, x, y);
-    else if (bs == 3)
-        hipLaunchKernelGGL((k_spmv<3, SPMV_U, false, int16_t>), dim3(grid), dim3(256), 0, S(stream), ns, nrows,
-                           slice_ptr, dcols, vals, x, y);
-    else {
-        set_error("fem_spmv16: block size %d unsupported", bs);
-        return FEM_EARG;
-    }
-    FEM_LAUNCHED();
-    return FEM_OK;
+    return spmv_plain("fem_spmv16", nrows, bs, slice_ptr, dcols, vals, x, y, stream);
 }
 
 // validate the caller's constraint arrays against [0, n) on `stream` (one sync) and fill c (tmp not allocated)
@@ -3368,59 +3469,6 @@ int fem_pcg_uniform_slices(fem_pcg* s, int64_t s_begin, int64_t s_end, int64_t* 
 
 static size_t pk_sync_words(int G) { return (size_t)(18 + G) * PK_LINE; }
 
-// distributed builds: 4 register slots per wave when the rank's slices fit (every rank of a 10M-tet system at
-// N >= 2: fewer loop-carried registers, no spills), else 7
-constexpr int PK_MAXS_DIST = 4;
-static const void* persist_fn_dist(bool prof, int maxs) {
-    if (!prof && maxs <= 1) return (const void*)k_pcg_persist<1, false, true, false, true>;   // 8 pairs in flight
-    if (!prof && maxs == 2) return (const void*)k_pcg_persist<2, false, true, false, true>;   // 4 pairs in flight
-    if (maxs <= PK_MAXS_DIST)
-        return prof ? (const void*)k_pcg_persist<PK_MAXS_DIST, true, true, false, true>
-                    : (const void*)k_pcg_persist<PK_MAXS_DIST, false, true, false, true>;
-    return prof ? (const void*)k_pcg_persist<PK_MAXS, true, true, false, true>
-                : (const void*)k_pcg_persist<PK_MAXS, false, true, false, true>;
-}
-static int dist_maxs(const fem_pcg* s) {
-    const int64_t nloc = s->pd_split[s->pd_rank + 1] - s->pd_split[s->pd_rank];
-    const int64_t maxL = (nloc + s->pk_grid - 1) / s->pk_grid;
-    return (int)((maxL + PK_WAVES - 1) / PK_WAVES);
-}
-
-// small: slices per wave of the packed assignment (1, 2, 3-4 select the one-, two-, four-slot build with 8, 4, 4 lane
-// pairs in flight; 0 the 7-slot build with 2)
-// od: the build that streams the diagonal-free values (FEM_TUNE_PK_OFFDIAG), one per build below
-static const void* persist_fn(bool prof, bool gsc1, bool ovf = false, int small = 0, bool od = false) {
-    if (od) {
-        if (small >= 1 && small <= 4 && !prof && !ovf && gsc1)
-            return small == 1 ? (const void*)k_pcg_persist<1, false, true, false, false, true>
-                 : small == 2 ? (const void*)k_pcg_persist<2, false, true, false, false, true>
-                              : (const void*)k_pcg_persist<4, false, true, false, false, true>;
-        if (ovf) return gsc1 ? (const void*)k_pcg_persist<PK_MAXS, false, true, true, false, true>
-                             : (const void*)k_pcg_persist<PK_MAXS, false, false, true, false, true>;
-        if (prof) return gsc1 ? (const void*)k_pcg_persist<PK_MAXS, true, true, false, false, true>
-                              : (const void*)k_pcg_persist<PK_MAXS, true, false, false, false, true>;
-        return gsc1 ? (const void*)k_pcg_persist<PK_MAXS, false, true, false, false, true>
-                    : (const void*)k_pcg_persist<PK_MAXS, false, false, false, false, true>;
-    }
-    if (small >= 1 && small <= 4 && !prof && !ovf && gsc1)
-        return small == 1 ? (const void*)k_pcg_persist<1, false, true>
-             : small == 2 ? (const void*)k_pcg_persist<2, false, true>
-                          : (const void*)k_pcg_persist<4, false, true>;
-    if (ovf) return gsc1 ? (const void*)k_pcg_persist<PK_MAXS, false, true, true>
-                         : (const void*)k_pcg_persist<PK_MAXS, false, false, true>;
-    if (prof) return gsc1 ? (const void*)k_pcg_persist<PK_MAXS, true, true> : (const void*)k_pcg_persist<PK_MAXS, true, false>;
-    return gsc1 ? (const void*)k_pcg_persist<PK_MAXS, false, true> : (const void*)k_pcg_persist<PK_MAXS, false, false>;
-}
-
-// bs = 3 (pcg_persist3.hpp): P3_MAXS slices per wave on chip, the overflow build past that (single GPU), the DIST
-// build when the rank's slices fit
-static const void* persist3_fn(bool ovf, bool dist) {
-    if (dist) return (const void*)k_pcg_persist3<P3_MAXS, false, true>;
-    return ovf ? (const void*)k_pcg_persist3<P3_MAXS, true> : (const void*)k_pcg_persist3<P3_MAXS, false>;
-}
-static size_t persist_lds(const fem_pcg* s) { return s->bs == 3 ? P3_LDS : PK_LDS; }
-static int persist_maxs(const fem_pcg* s) { return s->bs == 3 ? P3_MAXS : PK_MAXS; }
-
 // schedule 3 prerequisites: bs = 1 (lane-paired copy) or bs = 3 (plane-paired copy), 16-bit columns, single GPU, no
 // projections, capacity (every wave <= MAXS slices, else the overflow build), one resident PK_T-thread workgroup per CU
 static int persist_setup_dist(fem_pcg* s);
@@ -3463,8 +3511,7 @@ int fem_pcg_offdiag_slices(fem_pcg* s, int64_t* od_slices, int64_t* nslices, int
     int64_t c = 0;
     if (s->pk_ovf) {   // overflow build: only the register slots' slices (the first PK_MAXS of every wave's `pack`)
         const int G = s->pk_grid;
-        const int64_t maxL = (s->nslices + G - 1) / G;
-        const int64_t m = (maxL + PK_WAVES - 1) / PK_WAVES;
+        const int64_t m = pk_pack(s->nslices, G);
         for (int L = 0; L < G; ++L) {
             const int64_t sL0 = (int64_t)L * s->nslices / G, nL = (int64_t)(L + 1) * s->nslices / G - sL0;
             for (int wv = 0; wv < PK_WAVES; ++wv) {
@@ -3507,7 +3554,8 @@ static int persist_setup(fem_pcg* s) {
     const int G = (ncu / NXCD) * NXCD;
     if (G < NXCD) return FEM_OK;
     // past MAXS slices per wave: the overflow build (packed assignment only; overflow rows streamed from HBM)
-    const bool ovf = s->nslices > (int64_t)G * PK_WAVES * persist_maxs(s);
+    const PkFamily fam = s->bs == 3 ? PKF_BS3 : PKF_BS1;
+    const bool ovf = s->nslices > (int64_t)G * PK_WAVES * pk_max_slots(fam);
     if (ovf && (!(s->tune & FEM_TUNE_PK_PACK) || s->persist_fit_only)) return FEM_OK;
     // residency of every build, queried once per device and block size (host calls of ~tens of us per solve)
     // (the entry is published only after every build's attribute call succeeded, under a lock: a setup that fails
@@ -3519,18 +3567,9 @@ static int persist_setup(fem_pcg* s) {
         std::lock_guard<std::mutex> lk(occ_mu);
         int& slot = occ_cache[s->bs == 3][dev & 63];
         if (slot == 0) {
-            int res = 1;
-            for (int vv = 0; vv < (s->bs == 3 ? 2 : 18) && res == 1; ++vv) {
-                const int v = vv % 9;
-                const bool od = vv >= 9;   // the diagonal-free builds
-                const void* f = s->bs == 3 ? persist3_fn(v == 1, false)
-                              : v >= 6 ? persist_fn(false, true, false, v == 8 ? 4 : v - 5, od)
-                                       : persist_fn((v & 1) && v < 4, v & 2, v >= 4, 0, od);
-                FEM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)persist_lds(s)));
-                int nb = 0;
-                FEM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, PK_T, persist_lds(s)));
-                if (nb < 1) res = 2;
-            }
+            int res = 0;
+            const int rc = family_resident(fam, false, &res);
+            if (rc) return rc;
             slot = res;
         }
         occ = slot;
@@ -3566,22 +3605,15 @@ static int persist_setup(fem_pcg* s) {
     s->persist = 1;
     s->pk_gv = 0;
     if ((s->tune & FEM_TUNE_PK_GV) && (s->tune & FEM_TUNE_PK_SC1) && s->bs == 1 && !ovf && s->mode == FEM_MODE_PCG) {
-        const int64_t maxL = (s->nslices + G - 1) / G;
-        const int pack = (int)((maxL + PK_WAVES - 1) / PK_WAVES);
-        if (pack <= GV_MAXS) {
+        if (pk_pack(s->nslices, G) <= pk_max_slots(PKF_GV)) {
             static std::mutex gv_mu;
             static int gv_ok[64] = {};   // per device: 0 unknown, 1 resident, 2 not
             std::lock_guard<std::mutex> lk(gv_mu);
             int& slot = gv_ok[dev & 63];
             if (slot == 0) {
-                int res = 1;
-                for (int v = 0; v < 2 && res == 1; ++v) {
-                    const void* f = v ? (const void*)k_pcg_persist_gv<2> : (const void*)k_pcg_persist_gv<1>;
-                    FEM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GV_LDS));
-                    int nb = 0;
-                    FEM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, PK_T, GV_LDS));
-                    if (nb < 1) res = 2;
-                }
+                int res = 0;
+                const int rc = family_resident(PKF_GV, false, &res);
+                if (rc) return rc;
                 slot = res;
             }
             s->pk_gv = slot == 1;
@@ -3604,34 +3636,29 @@ static int persist_setup_dist(fem_pcg* s) {
         return FEM_EARG;
     }
     const int G = s->pk_grid;
-    const int64_t nloc = s->pd_split[s->pd_rank + 1] - s->pd_split[s->pd_rank];
-    if ((nloc + G - 1) / G > (int64_t)PK_WAVES * persist_maxs(s)) {
+    const int64_t nloc = pk_own_slices(s);
+    if ((nloc + G - 1) / G > (int64_t)PK_WAVES * pk_max_slots(s->bs == 3 ? PKF_BS3 : PKF_BS1_DIST)) {
         set_error("distributed persistent PCG: %lld slices on this rank exceed the register capacity of %d workgroups",
                   (long long)nloc, G);
         return FEM_EARG;
     }
-    for (int v = 0; v < (s->bs == 3 ? 1 : 2); ++v) {
-        const void* f = s->bs == 3 ? persist3_fn(false, true) : persist_fn_dist(v == 1, dist_maxs(s));
-        FEM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)persist_lds(s)));
+    s->pk_ovf = 0;
+    s->pk_gv = 0;
+    for (int prof = 0; prof < (s->bs == 3 ? 1 : 2); ++prof) {   // this rank's build and (bs = 1) its instrumented form
+        const PkBuild* b = persist_plan(s, prof != 0, false).b;
         int nb = 0;
-        FEM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, PK_T, persist_lds(s)));
+        const int rc = b ? check_resident(b->fn, PK_T, b->lds, &nb) : FEM_OK;
+        if (rc) return rc;
         if (nb < 1) {
             set_error("distributed persistent PCG: kernel does not fit one workgroup per CU");
             return FEM_EARG;
         }
     }
-    s->pk_ovf = 0;
     s->persist = 1;
-    s->pk_gv = 0;
-    if (s->pd_off_m1 > 0 && s->mode == FEM_MODE_PCG && dist_maxs(s) <= GV_MAXS) {   // pipelined DIST build
-        int res = 1;
-        for (int v = 0; v < 2 && res == 1; ++v) {
-            const void* f = v ? (const void*)k_pcg_persist_gv<2, true> : (const void*)k_pcg_persist_gv<1, true>;
-            FEM_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GV_LDS));
-            int nb = 0;
-            FEM_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, f, PK_T, GV_LDS));
-            if (nb < 1) res = 2;
-        }
+    if (s->pd_off_m1 > 0 && s->mode == FEM_MODE_PCG && pk_pack(nloc, G) <= pk_max_slots(PKF_GV)) {   // pipelined DIST
+        int res = 0;
+        const int rc = family_resident(PKF_GV, true, &res);
+        if (rc) return rc;
         s->pk_gv = res == 1;
     }
     return FEM_OK;
@@ -3643,6 +3670,70 @@ static int persist_reset_sync(fem_pcg* s) {
     FEM_HIP(hipMemsetAsync(&s->st->pk_epoch, 0, sizeof(unsigned), s->stream));
     s->pk_epochs = 0;
     return FEM_OK;
+}
+
+// the kernel arguments of one launch of plan.b: every field is assigned here and nowhere else
+static PkArgs pk_args(const fem_pcg* s, const PkPlan& plan, int k, unsigned long long* prof) {
+    const bool bs3 = s->bs == 3;   // plane-paired values, per-lane 16-bit node deltas (no slice-uniform lists)
+    const bool uni = (s->tune & FEM_TUNE_PK_UNI) && s->puoff;
+    const bool od = plan.b->od;    // the context's diagonal-free stream instead of the shared values and lists
+    PkArgs a;
+    a.nslices = pk_own_slices(s);
+    a.nrows = s->nrows;
+    a.slice_ptr = s->slice_ptr;
+    a.cols = pcols(s);
+    a.vals = od ? s->pk_ovals : s->pvals;
+    a.uoff = uni && !bs3 ? s->puoff : nullptr;
+    a.ucol = bs3 ? nullptr : od ? s->pk_oucol : uni ? s->pucol : nullptr;
+    a.x = s->x;
+    a.r = s->r;
+    a.p = s->p0;
+    a.s = s->p1;
+    a.u = s->pd ? reinterpret_cast<double*>(s->pd_block) : s->q;
+    a.w = s->w;
+    a.win = s->pk_win;
+    a.part = s->pk_part;
+    a.sync = s->pk_sync;
+    a.st = s->st;
+    a.hist = s->hist;
+    a.hist_len = s->hist_len;
+    a.kmax = k;
+    a.rev = (s->tune & FEM_TUNE_REVERSE) ? 1 : 0;
+    a.prof = prof;
+    a.v = s->pk_ovf ? s->pk_v : nullptr;
+    a.pack = plan.pack;
+    // distributed: this rank's slices (above), the comm blocks, the init on the first launch after start
+    a.sbase = s->pd ? s->pd_split[s->pd_rank] : 0;
+    a.rank = s->pd ? s->pd_rank : 0;
+    a.nranks = s->pd ? s->pd_nranks : 1;
+    for (int q = 0; q < PK_MAX_RANKS; ++q) a.peer[q] = s->pd && q < s->pd_nranks ? s->pd_peer[q] : nullptr;
+    a.off_flag = s->pd ? s->pd_off_flag : 0;
+    a.off_red = s->pd ? s->pd_off_red : 0;
+    a.off_rflag = s->pd ? s->pd_off_rflag : 0;
+    a.pub = s->pd ? s->pd_pub : nullptr;
+    a.b = s->b;
+    a.init = s->pd ? s->pd_init_pending : 0;
+    a.diag = od ? s->pk_diag : nullptr;
+    a.vals_full = s->pvals;
+    a.ucol_full = uni ? s->pucol : nullptr;
+    return a;
+}
+
+// the pipelined kernel's second argument: its vectors in gv_buf; distributed, the gathered m lives in the comm blocks
+// (m[0] the u region, m[1] after it) and PkArgs::init starts the solve
+static GvArgs gv_args(const fem_pcg* s) {
+    const int64_t n = s->n;
+    GvArgs g;
+    g.u = s->gv_buf;
+    g.w = s->gv_buf + n;
+    g.q = s->gv_buf + 2 * n;
+    g.z = s->gv_buf + 3 * n;
+    g.m[0] = s->pd ? reinterpret_cast<double*>(s->pd_block) : s->gv_buf + 4 * n;
+    g.m[1] = s->pd ? reinterpret_cast<double*>(s->pd_block + s->pd_off_m1) : s->gv_buf + 5 * n;
+    g.moff[0] = 0;
+    g.moff[1] = s->pd ? s->pd_off_m1 : 0;
+    g.init = s->pd ? 0 : s->gv_init_pending;
+    return g;
 }
 
 static int launch_persist(fem_pcg* s, int k, unsigned long long* prof) {
@@ -3658,138 +3749,36 @@ static int launch_persist(fem_pcg* s, int k, unsigned long long* prof) {
         if (rc) return rc;
     }
     s->pk_epochs += k + 1;
-    PkArgs a;
-    a.nslices = s->nslices;
-    a.nrows = s->nrows;
-    a.slice_ptr = s->slice_ptr;
-    a.cols = s->pcols16;
-    a.vals = s->pvals;
-    const bool uni = (s->tune & FEM_TUNE_PK_UNI) && s->puoff;
-    a.uoff = uni ? s->puoff : nullptr;
-    a.ucol = uni ? s->pucol : nullptr;
-    a.x = s->x;
-    a.r = s->r;
-    a.p = s->p0;
-    a.s = s->p1;
-    a.u = s->q;
-    a.w = s->w;
-    a.win = s->pk_win;
-    a.part = s->pk_part;
-    a.sync = s->pk_sync;
-    a.st = s->st;
-    a.hist = s->hist;
-    a.hist_len = s->hist_len;
-    a.kmax = k;
-    a.rev = (s->tune & FEM_TUNE_REVERSE) ? 1 : 0;
-    a.prof = prof;
-    a.v = s->pk_ovf ? s->pk_v : nullptr;
-    {   // packed slice assignment: m = ceil(max slices of a workgroup / waves) per wave
-        const int64_t maxL = (s->nslices + G - 1) / G;
-        a.pack = (s->tune & FEM_TUNE_PK_PACK) ? (int)((maxL + PK_WAVES - 1) / PK_WAVES) : 0;
+    const bool gv = s->pk_gv && s->bs == 1;   // pipelined (pcg_persist_gv.hpp)
+    if (prof && (gv || (s->bs == 3 && !s->pd))) {
+        set_error("persistent PCG: no instrumented (PROF) build %s", gv ? "of the pipelined iteration" : "for bs = 3");
+        return FEM_EARG;
     }
-    a.sbase = 0;
-    a.rank = 0;
-    a.nranks = 1;
-    for (int q = 0; q < PK_MAX_RANKS; ++q) a.peer[q] = nullptr;
-    a.off_flag = a.off_red = a.off_rflag = 0;
-    a.pub = nullptr;
-    a.b = s->b;
-    a.init = 0;
-    a.diag = nullptr;
-    a.vals_full = a.vals;
-    a.ucol_full = a.ucol;
-    const bool od = s->pk_od && s->bs == 1 && !s->pd && !s->pk_gv;
-    if (od) {   // the context's diagonal-free stream instead of the shared values and lists
-        a.vals = s->pk_ovals;
-        a.ucol = s->pk_oucol;
-        a.diag = s->pk_diag;
+    if (s->pd && !prof && !gv) prof = s->pd_prof;   // fem_pcg_set_prof
+    if (s->bs == 3) prof = nullptr;                 // (no instrumented bs = 3 build: the DIST one runs plain)
+    const PkPlan plan = persist_plan(s, prof != nullptr);
+    if (!plan.b) {
+        set_error("persistent PCG: no build for this context (%d slices per wave)", plan.pack);
+        return FEM_ESTATE;
     }
-    if (s->pd) {   // distributed: this rank's slices, comm blocks, the init on the first launch after start
-        const int64_t S0 = s->pd_split[s->pd_rank], S1 = s->pd_split[s->pd_rank + 1];
-        a.nslices = S1 - S0;
-        a.sbase = S0;
-        a.rank = s->pd_rank;
-        a.nranks = s->pd_nranks;
-        for (int q = 0; q < s->pd_nranks; ++q) a.peer[q] = s->pd_peer[q];
-        a.off_flag = s->pd_off_flag;
-        a.off_red = s->pd_off_red;
-        a.off_rflag = s->pd_off_rflag;
-        a.pub = s->pd_pub;
-        a.u = reinterpret_cast<double*>(s->pd_block);
-        a.init = s->pd_init_pending;
-        s->pd_init_pending = 0;
-        const int64_t maxL = (a.nslices + G - 1) / G;
-        a.pack = (int)((maxL + PK_WAVES - 1) / PK_WAVES);
+    PkArgs a = pk_args(s, plan, k, prof);
+    s->pd_init_pending = 0;   // (a.init)
+    GvArgs g;
+    void* args[] = {&a, &g};   // k_pcg_persist / k_pcg_persist3 take a alone
+    if (gv) {
+        g = gv_args(s);
+        s->gv_init_pending = 0;   // (g.init)
+        s->pk_epochs += 2;        // the init barriers
     }
-    if (s->pk_gv && s->bs == 1) {   // pipelined (pcg_persist_gv.hpp): packed slices, <= GV_MAXS per wave
-        if (prof) {
-            set_error("persistent PCG: no instrumented (PROF) build of the pipelined iteration");
-            return FEM_EARG;
-        }
-        if (!s->pd) {
-            const int64_t maxL = (s->nslices + G - 1) / G;
-            a.pack = (int)((maxL + PK_WAVES - 1) / PK_WAVES);
-        }   // (distributed: this rank's packing, set above)
-        const int64_t n = s->n;
-        GvArgs g;
-        g.u = s->gv_buf;
-        g.w = s->gv_buf + n;
-        g.q = s->gv_buf + 2 * n;
-        g.z = s->gv_buf + 3 * n;
-        if (s->pd) {   // the gathered m in the comm blocks: m[0] the u region, m[1] after it
-            g.m[0] = reinterpret_cast<double*>(s->pd_block);
-            g.m[1] = reinterpret_cast<double*>(s->pd_block + s->pd_off_m1);
-            g.moff[0] = 0;
-            g.moff[1] = s->pd_off_m1;
-            g.init = 0;   // (a.init)
-        } else {
-            g.m[0] = s->gv_buf + 4 * n;
-            g.m[1] = s->gv_buf + 5 * n;
-            g.moff[0] = g.moff[1] = 0;
-            g.init = s->gv_init_pending;
-            s->gv_init_pending = 0;
-        }
-        s->pk_epochs += 2;   // the init barriers
-        void* gargs[] = {&a, &g};
-        const void* gfn = s->pd ? (a.pack <= 1 ? (const void*)k_pcg_persist_gv<1, true> : (const void*)k_pcg_persist_gv<2, true>)
-                                : (a.pack <= 1 ? (const void*)k_pcg_persist_gv<1> : (const void*)k_pcg_persist_gv<2>);
-        if (s->pk_coop || (s->tune & FEM_TUNE_PK_COOP))
-            FEM_HIP(hipLaunchCooperativeKernel(gfn, dim3(G), dim3(PK_T), gargs, GV_LDS, s->stream));
-        else
-            FEM_HIP(hipLaunchKernel(gfn, dim3(G), dim3(PK_T), gargs, GV_LDS, s->stream));
-        FEM_LAUNCHED();
-        s->launched += k;
-        return FEM_OK;
-    }
-    void* args[] = {&a};
-    if (s->pd && !prof && s->pd_prof) a.prof = prof = s->pd_prof;
-    if (s->bs == 3) {   // plane-paired values, per-lane 16-bit node deltas; no instrumented build
-        if (prof && !s->pd) {
-            set_error("persistent PCG: no instrumented (PROF) build for bs = 3");
-            return FEM_EARG;
-        }
-        a.cols = s->cols16;
-        a.uoff = nullptr;
-        a.ucol = nullptr;
-        a.prof = nullptr;
-        if (!s->pd) {   // k_pcg_persist3 always takes the packed assignment
-            const int64_t maxL = (s->nslices + G - 1) / G;
-            a.pack = (int)((maxL + PK_WAVES - 1) / PK_WAVES);
-        }
-    }
-    const void* fn = s->bs == 3 ? persist3_fn(s->pk_ovf != 0, s->pd != 0)
-                   : s->pd ? persist_fn_dist(prof != nullptr, a.pack)
-                           : persist_fn(prof != nullptr && !s->pk_ovf, (s->tune & FEM_TUNE_PK_SC1) != 0, s->pk_ovf != 0,
-                                        (a.pack <= 4 && !(s->tune & FEM_TUNE_PK_WIDE)) ? a.pack : 0, od);
     // the grid spins on inter-workgroup flags, so all G workgroups must be resident together: one per CU is
     // what the occupancy query promised, and a cooperative launch makes the runtime guarantee it (or fail) even
     // when other streams / processes hold CUs. A plain launch (the bench's fixed-iteration runs) relies on the
     // occupancy check; should residency still fail, every spin is bounded and the launch ends with
     // FEM_PCG_SYNC_TIMEOUT (fem_pcg_solve then re-solves on the deferred schedule).
     if (s->pk_coop || (s->tune & FEM_TUNE_PK_COOP))
-        FEM_HIP(hipLaunchCooperativeKernel(fn, dim3(G), dim3(PK_T), args, persist_lds(s), s->stream));
+        FEM_HIP(hipLaunchCooperativeKernel(plan.b->fn, dim3(G), dim3(PK_T), args, plan.b->lds, s->stream));
     else
-        FEM_HIP(hipLaunchKernel(fn, dim3(G), dim3(PK_T), args, persist_lds(s), s->stream));
+        FEM_HIP(hipLaunchKernel(plan.b->fn, dim3(G), dim3(PK_T), args, plan.b->lds, s->stream));
     FEM_LAUNCHED();
     s->launched += k;
     return FEM_OK;
@@ -3805,23 +3794,10 @@ int fem_pcg_persist_build(fem_pcg* s, int* slots, int* overflow, int* pack) {
     *overflow = 0;
     *pack = 0;
     if (!s->persist || s->pk_grid <= 0) return FEM_OK;
-    const int G = s->pk_grid;
-    int64_t ns = s->nslices;
-    if (s->pd) ns = s->pd_split[s->pd_rank + 1] - s->pd_split[s->pd_rank];
-    const int64_t maxL = (ns + G - 1) / G;
-    const int pk = (int)((maxL + PK_WAVES - 1) / PK_WAVES);
+    const PkPlan plan = persist_plan(s, false, false);   // the single-reduction build, also of a pipelined context
+    *slots = plan.b ? plan.b->slots : 0;
     *overflow = s->pk_ovf;
-    *pack = (s->bs == 3 || s->pd || (s->tune & FEM_TUNE_PK_PACK)) ? pk : 0;
-    // the same selection as launch_persist (persist_fn / persist_fn_dist / persist3_fn, non-instrumented)
-    if (s->bs == 3) {
-        *slots = P3_MAXS;
-    } else if (s->pd) {
-        *slots = pk <= 1 ? 1 : pk == 2 ? 2 : pk <= PK_MAXS_DIST ? PK_MAXS_DIST : PK_MAXS;
-    } else {
-        const int small = (*pack <= 4 && !(s->tune & FEM_TUNE_PK_WIDE)) ? *pack : 0;
-        *slots = (small >= 1 && small <= 4 && !s->pk_ovf && (s->tune & FEM_TUNE_PK_SC1))
-                     ? (small == 1 ? 1 : small == 2 ? 2 : 4) : PK_MAXS;
-    }
+    *pack = plan.pack;
     return FEM_OK;
 }
 
@@ -3915,6 +3891,20 @@ static int refresh_pairing(fem_pcg* s) {
     return FEM_OK;
 }
 
+// the pipelined iteration's vectors u, w, q, z, m[0], m[1] ([6 n]), zeroed for every solve
+static int gv_ensure(fem_pcg* s) {
+    const int64_t need = 6 * s->n;
+    if (need > s->gv_cap) {
+        pool_free(s->gv_buf, s->stream);
+        s->gv_buf = nullptr;
+        s->gv_cap = 0;
+        FEM_HIP(pool_alloc((void**)&s->gv_buf, sizeof(double) * (size_t)need, s->stream, true));
+        s->gv_cap = need;
+    }
+    FEM_HIP(hipMemsetAsync(s->gv_buf, 0, sizeof(double) * (size_t)need, s->stream));
+    return FEM_OK;
+}
+
 int fem_pcg_start(fem_pcg* s) {
     if (s->mf && s->dist && !s->cg1) {   // fem_pcg_set_dist resets the variant to 0: refuse at setup, not at phase 0
         set_error("fem_pcg_start: a distributed element-chunk context needs the single-reduction variant "
@@ -3967,45 +3957,16 @@ int fem_pcg_start(fem_pcg* s) {
         s->pk_epochs = 0;
         s->pd_init_pending = 1;
         s->launched = 0;
-        if (s->pk_gv) {   // pipelined: its vectors u, w, q, z (global length); m lives in the comm block
-            const int64_t need = 6 * s->n;
-            if (need > s->gv_cap) {
-                pool_free(s->gv_buf, s->stream);
-                s->gv_buf = nullptr;
-                s->gv_cap = 0;
-                FEM_HIP(pool_alloc((void**)&s->gv_buf, sizeof(double) * (size_t)need, s->stream, true));
-                s->gv_cap = need;
-            }
-            FEM_HIP(hipMemsetAsync(s->gv_buf, 0, sizeof(double) * (size_t)need, s->stream));
-        }
+        // pipelined: its vectors u, w, q, z (global length); m lives in the comm block
+        if (s->pk_gv && (rc = gv_ensure(s))) return rc;
         return FEM_OK;   // every rank must finish its start before any rank launches (a host barrier)
     }
-    if (s->mf) {   // element-chunk operator: r0 = b - A x0 from the element formula
-        if ((rc = mf_apply(s->mf, s->x, s->q, s->mf_sl, s->stream))) return rc;
-    } else if (s->pext) {   // solver layout: r0 = b - A x0 from the paired values
-        if (s->bs == 1)
-            hipLaunchKernelGGL(k_spmv_pair<SPMV_UP>, dim3(s->grid_spmv), dim3(256), 0, s->stream, s->nslices, s->nrows,
-                               s->slice_ptr, s->pcols16, s->pvals, s->puoff, s->pucol, s->x, s->q);
-        else
-            hipLaunchKernelGGL(k_spmv_a, dim3(s->grid_spmv), dim3(256), 0, s->stream, s->nslices, s->nrows,
-                               s->slice_ptr, s->cols16, s->pvals, s->x, s->q);
-        FEM_LAUNCHED();
-    } else if ((rc = (s->cols16 ? fem_spmv16(s->nrows, s->bs, s->slice_ptr, s->cols16, s->vals, s->x, s->q, s->stream)
-                                 : fem_spmv(s->nrows, s->bs, s->slice_ptr, s->cols, s->vals, s->x, s->q, s->stream))))
-        return rc;
+    if ((rc = start_spmv(s, true))) return rc;   // r0 = b - A x0
     if (s->persist) {   // single-reduction start: r0 = b - A x0, u0 = w r0 (in q), p = s = 0, g0 -> red[1]
         const int zrc = persist_reset_sync(s);   // after the state upload: zeroes st->pk_epoch too
         if (zrc) return zrc;
         if (s->pk_gv) {   // pipelined: its vectors (q = z = 0; u, w, m formed by the first launch)
-            const int64_t need = 6 * s->n;
-            if (need > s->gv_cap) {
-                pool_free(s->gv_buf, s->stream);
-                s->gv_buf = nullptr;
-                s->gv_cap = 0;
-                FEM_HIP(pool_alloc((void**)&s->gv_buf, sizeof(double) * (size_t)need, s->stream, true));
-                s->gv_cap = need;
-            }
-            FEM_HIP(hipMemsetAsync(s->gv_buf, 0, sizeof(double) * (size_t)need, s->stream));
+            if ((rc = gv_ensure(s))) return rc;
             s->gv_init_pending = 1;
         }
         hipLaunchKernelGGL(k_cg1_init, dim3(s->grid_vec), dim3(PCG_BLOCK), 0, s->stream, s->n, s->bs, s->b, s->r,

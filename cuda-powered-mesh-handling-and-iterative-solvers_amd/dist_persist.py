@@ -173,6 +173,13 @@ class RankRunner:
         C.check(self.lib.fem_pcg_pipelined(self.h, ctypes.byref(on)), "fem_pcg_pipelined")
         return bool(on.value)
 
+    def persist_build(self):
+        """(register slots per wave, overflow build, packed slices per wave) of the started rank's launches."""
+        sl, ov, pk = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        C.check(self.lib.fem_pcg_persist_build(self.h, ctypes.byref(sl), ctypes.byref(ov), ctypes.byref(pk)),
+                "fem_pcg_persist_build")
+        return sl.value, ov.value, pk.value
+
     def debug(self, which, n):
         buf = (ctypes.c_int32 * n)()
         with C.device_scope(self.device):

@@ -74,6 +74,47 @@ def test_dist_persist_fixed_iterations_and_chunks(gpu):
     assert torch.equal(xs[0], xs[1]) and torch.equal(xs[0], xs[2])
 
 
+_DIST_SLOTS = {}   # n -> slot counts of the ranks, for the cross-size assertion of the last case
+
+
+@pytest.mark.parametrize("n", [24, 70, 90])
+def test_dist_persist_slot_selection(gpu, n):
+    """The DIST builds by register slots: two emulated ranks own about 123, 2,797 and 5,888 slices at n = 24, 70, 90,
+    which on 128 workgroups each is 1, 2 and 3 packed slices per wave -> the 1-, 2- and 4-slot builds. Every rank
+    reports (slots, 0, pack) as computed here from its own slice count and grid; 24 fixed iterations match the
+    single-GPU persistent schedule."""
+    C, DP, mesh, system = _mods()
+    c, t, b, mask, A, w = _case(mesh, system, n, gpu)
+    run = system.PcgRunner(A, b, w, tol=0.0, schedule=3)
+    run.start()
+    run.iterate(24)
+    assert run.poll()[0] == 24
+    x1 = run.x.clone()
+    run.close()
+    ncu = torch.cuda.get_device_properties(gpu).multi_processor_count
+    G = (ncu // 2) // 8 * 8
+    grp = DP.EmulatedGroup(c, t, 2, b, fixed_mask=mask, tol=0.0)
+    try:
+        grp.start()
+        slots = []
+        for r, rr in enumerate(grp.ranks):
+            nloc = grp.split[r + 1] - grp.split[r]
+            pack = -(-(-(-nloc // G)) // 16)
+            want = 1 if pack == 1 else 2 if pack == 2 else 4 if pack <= 4 else 7
+            assert rr.effective_schedule() == system.SCHED_PERSIST
+            assert rr.persist_build() == (want, 0, pack), (r, nloc, G, rr.persist_build())
+            slots.append(want)
+        grp.iterate(24)
+        it, stt, _ = grp.poll()
+        assert it == 24 and stt == C.PCG_RUNNING
+        assert rel(grp.x(), x1) < 1e-12
+    finally:
+        grp.close()
+    _DIST_SLOTS[n] = tuple(slots)
+    if ncu == 256 and len(_DIST_SLOTS) == 3:   # the three sizes reached three different builds
+        assert [_DIST_SLOTS[m] for m in (24, 70, 90)] == [(1, 1), (2, 2), (4, 4)], _DIST_SLOTS
+
+
 def test_dist_persist_cg_mode_and_initial_guess(gpu):
     """CG mode (0/1 weights, masked rows) and a non-zero x0: the distributed init forms r0 = b - A x0 in-kernel."""
     C, DP, mesh, system = _mods()

@@ -972,6 +972,7 @@ def test_persistent_full_geometry_10m(gpu):
     run = system.PcgRunner(A, b, w, tol=0.0, schedule=3)
     run.set_tuning(1 | 2 | 8)   # REVERSE | PAIR | PK_PACK, without PK_SC1
     run.start()
+    assert run.persist_build()[0] == 7   # the 1-, 2- and 4-slot builds need the sc1 gathers
     run.iterate(50)
     assert run.poll()[0] == 50 and torch.equal(run.x, xs[1][1])
     run.close()

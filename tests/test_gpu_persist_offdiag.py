@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 F64 = torch.float64
 OFFDIAG = 32768   # FEM_TUNE_PK_OFFDIAG
 WIDE = 256        # FEM_TUNE_PK_WIDE
+SC1 = 4           # FEM_TUNE_PK_SC1
 
 
 def _mods():
@@ -133,6 +134,35 @@ def test_every_build(gpu, n, wide):
     assert torch.equal(x1, x0) and p1 == p0
     x3 = A.pcg(b, w=w, mode=C.MODE_PCG, tol=0.0, max_iter=k, schedule=0).x
     assert rel(x1, x3) < 1e-12
+
+
+@pytest.mark.parametrize("drop", [0, OFFDIAG, SC1], ids=["default", "offdiag_off", "sc1_off"])
+def test_instrumented_builds(gpu, drop):
+    """The phase-clock (PROF) builds, which otherwise run only from tools/: 24 fixed iterations through
+    fem_pcg_persist_profile with the default flags, without the diagonal-free stream and without the sc1 gathers.
+    The clocks tick, and x equals bit for bit the plain run of the same 7-slot build (FEM_TUNE_PK_WIDE)."""
+    import ctypes
+    C, _, _, system = _mods()
+    A, b, w, _, _ = _cube20(gpu)
+    flags = C.TUNE_DEFAULT & ~drop
+    G = torch.cuda.get_device_properties(0).multi_processor_count // 8 * 8   # one workgroup per CU
+    run = system.PcgRunner(A, b, w, tol=0.0, schedule=3)
+    try:
+        run.set_tuning(flags)
+        run.start()
+        assert run.effective_schedule() == 3
+        buf = (ctypes.c_ulonglong * (G * (8 + 16)))()   # [G][8 phases] then [G][16 waves]
+        g = ctypes.c_int()
+        C.check(run.lib.fem_pcg_persist_profile(run.h, 24, buf, ctypes.byref(g)), "fem_pcg_persist_profile")
+        poll = run.poll()
+        x = run.x.clone()
+    finally:
+        run.close()
+    assert g.value == G
+    assert poll[0] == 24 and poll[1] == 0
+    assert buf[1] != 0   # workgroup 0, phase 1: the SpMV
+    _, _, x0 = _run(A, b, w, flags | WIDE, (24,))
+    assert torch.equal(x, x0)
 
 
 def test_no_qualifying_slice(gpu):
