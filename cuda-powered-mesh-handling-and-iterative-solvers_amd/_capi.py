@@ -193,6 +193,16 @@ SIGNATURES = {
     "fem_mpcg_solve": (_I, [_P, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_D)]),
     "fem_mpcg_scalars": (_I, [_P, ctypes.POINTER(_D)]),
     "fem_mpcg_destroy": (None, [_P]),
+    "fem_coarse_restrict": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "fem_coarse_apply": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fem_coarse_galerkin_count": (_I, [_L, _I, _P, _P, _P, _P, _P, _P]),
+    "fem_coarse_galerkin": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "fem_coarse_galerkin_sum": (_I, [_L, _I, _P, _P, _P, _P, _P, _P]),
+    "fem_pcg2_create": (_I, [_L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _D, _P, _L, _P,
+                             ctypes.POINTER(_P)]),
+    "fem_pcg2_solve": (_I, [_P, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_D)]),
+    "fem_pcg2_scalars": (_I, [_P, ctypes.POINTER(_D)]),
+    "fem_pcg2_destroy": (None, [_P]),
     "fem_spmm_km": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "fem_modal_work_len": (_L, []),
     "fem_modal_gram": (_I, [_L, _I, _I, ctypes.POINTER(_P), _P, _P, _P]),

@@ -323,13 +323,21 @@ def _static_with_shells(coords, force, fixed, c3d4, c3d6, c3d8, s3, s4, material
 
 # ============================================================================ fused mesh -> solution pipeline
 def solve_tet4(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, tol=1e-8, max_iter=10000, device="cuda:0",
-               rtol=None, reorder=None, operator="assembled"):
+               rtol=None, reorder=None, operator="assembled", preconditioner="jacobi", n_aggregates=None):
     """Assembly + Jacobi-PCG straight from the mesh (the benchmark pipeline; no element matrices stored):
     c3d4 Poisson (dpn 1, kappa = E) or elasticity (dpn 3), Dirichlet zero on `fixed` nodes via zeros in the
     exact Jacobi M_inv, reference PCG semantics (absolute tol on sqrt(r.z); `rtol` scales it by sqrt(r0.z0)).
     reorder="rcm": solve on the reverse Cuthill-McKee renumbering of the nodes (system.rcm_order; for meshes in
     file order) and return u in the caller's numbering (the returned SellMatrix is the renumbered one).
+    preconditioner="two-level" (kind="elastic", operator="assembled" only): the Jacobi weights plus the rigid-body
+    coarse correction over `n_aggregates` aggregates (SellMatrix.rigid_coarse_space / pcg_two_level; sqrt(r.z) is then
+    measured with the two-level z).
     Returns (u [N, dpn], PcgResult, SellMatrix)."""
+    if preconditioner not in ("jacobi", "two-level"):
+        raise ValueError(f"unknown preconditioner {preconditioner!r} (supported: 'jacobi', 'two-level')")
+    if preconditioner == "two-level" and (kind != "elastic" or operator != "assembled"):
+        raise ValueError("preconditioner='two-level' needs kind='elastic' and operator='assembled' "
+                         f"(got kind={kind!r}, operator={operator!r})")
     dev = _dev(device)
     coords = coords.to(device=dev, dtype=F64).contiguous()
     elements = elements.to(device=dev, dtype=LONG).contiguous()
@@ -354,13 +362,64 @@ def solve_tet4(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, tol=1e
     mask[fixed_mask] = 1
     w = A.jacobi(mask.view(-1))
     b = b.reshape(-1).contiguous().clone()
-    if rtol is not None:
-        tol = float(rtol) * float(torch.sqrt(torch.dot(b, w * b)))
-    res = A.pcg(b, None, w=w, mode=C.MODE_PCG, tol=tol, max_iter=max_iter)
+    if preconditioner == "two-level":
+        cs = A.rigid_coarse_space(coords, w, n_aggregates=n_aggregates)
+        if rtol is not None:
+            tol = float(rtol) * float(torch.sqrt(torch.dot(b, cs.apply(b))))
+        res = A.pcg_two_level(b, None, coarse=cs, tol=tol, max_iter=max_iter)
+        res.coarse = cs
+    else:
+        if rtol is not None:
+            tol = float(rtol) * float(torch.sqrt(torch.dot(b, w * b)))
+        res = A.pcg(b, None, w=w, mode=C.MODE_PCG, tol=tol, max_iter=max_iter)
     u = res.x.view(N, A.bs)
     if inv is not None:
         u = u[inv]
     return u, res, A
+
+
+# ============================================================================ two-level PCG
+def two_level_pcg_solver(K, elements, coords, F, fixed, u_init=None, tol=1e-8, rtol=None, max_iter=1000,
+                         n_aggregates=None, device="cuda:0", dtype=torch.float64, return_info=False):
+    """PCG on K u = F with M^-1 = diag(w) + Z (Z^T A Z)^-1 Z^T: the exact Jacobi weights w (zero on the dofs of the
+    `fixed` nodes, which are thereby held at their u_init value, zero by default) plus the rigid-body coarse correction
+    over `n_aggregates` aggregates of the free nodes (SellMatrix.rigid_coarse_space). K / elements are one solid family
+    with 3 dofs per node, or lists of families on the same nodes (as static_structure_solver assembles them). Stop on
+    sqrt(r.z) < tol (`rtol`: times sqrt(r0.z0)); prints preconditioned_conjugate_gradient_solver's messages. Returns
+    u [N, 3] (with return_info: (u, PcgResult), the CoarseSpace in `.coarse`)."""
+    dev = _dev(device)
+    coords = coords.to(device=dev, dtype=F64).contiguous()
+    N = coords.shape[0]
+    fams = list(zip(K, elements)) if isinstance(K, (list, tuple)) else [(K, elements)]
+    fams = [(k.to(device=dev, dtype=F64).contiguous(), el.to(device=dev, dtype=LONG).contiguous()) for k, el in fams]
+    for k, el in fams:
+        if k.shape[-1] != 3 * el.shape[1]:
+            raise ValueError(f"two_level_pcg_solver: 3 dofs per node are needed (element matrices of size "
+                             f"{k.shape[-1]} for {el.shape[1]} nodes)")
+    if tuple(F.shape) != (N, 3):
+        raise ValueError(f"two_level_pcg_solver: F must be [{N}, 3], got {list(F.shape)}")
+    if len(fams) == 1:
+        A = assemble(fams[0][0], fams[0][1], N, dev)
+    else:
+        g = _sys.build_graph(_sys.pad_connectivity([el for _, el in fams], max(el.shape[1] for _, el in fams)), N)
+        A = _sys.SellMatrix(g, 3)
+        for k, el in fams:
+            A.add_element_matrices(k, el, inc=_sys.incidence(el, N))
+    mask = torch.zeros((N, 3), dtype=torch.uint8, device=dev)
+    if fixed is not None:
+        mask[torch.as_tensor(fixed).to(device=dev, dtype=LONG)] = 1
+    w = A.jacobi(mask.view(-1))
+    cs = A.rigid_coarse_space(coords, w, n_aggregates=n_aggregates)
+    b = F.to(device=dev, dtype=F64).reshape(-1).contiguous()
+    x0 = None if u_init is None else u_init.to(device=dev, dtype=F64).reshape(-1).contiguous()
+    if rtol is not None:
+        r0 = b if x0 is None else b - A.matvec(x0)
+        tol = float(rtol) * float(torch.sqrt(torch.dot(r0, cs.apply(r0))))
+    res = A.pcg_two_level(b, x0, coarse=cs, tol=tol, max_iter=max_iter)
+    res.coarse = cs
+    _pcg_messages(res)
+    u = res.x.view(N, 3).to(device=torch.device(device), dtype=dtype)
+    return (u, res) if return_info else u
 
 
 # ============================================================================ several load cases per matrix

@@ -475,6 +475,137 @@ def uniform_slices(lib, h, s_begin=0, s_end=-1):
     return u.value, n.value, ib.value
 
 
+# Two-level PCG (csrc/pcg_coarse.hip): free nodes per aggregate of the default aggregation, and the most aggregates
+# (m = 6 k <= 3072: Einv is a dense [m, m] tensor that every iteration reads). COARSE_TARGET was chosen from time to
+# solution at the n = 55 and n = 119 cubes among 500, 1500 and 4000 (setup included: 96 / 46 / 40 ms at n = 55,
+# 275 / 275 / 294 ms at n = 119, where 500 and 1500 both reach the cap; DESIGN §8p, profiles/twolevel_n*.json).
+COARSE_TARGET = 1500
+COARSE_MAX_AGG = 512
+COARSE_DROP = 1e-10   # directions of an aggregate's Gram block below this fraction of its largest eigenvalue go
+
+
+class CoarseSpace:
+    """Rigid-body coarse space of a bs = 3 matrix (SellMatrix.rigid_coarse_space): k aggregates of free nodes, six
+    modes each, Z never stored. `E` is Z^T A Z as the Galerkin kernels sum it (not symmetrised), `Einv` the symmetric
+    T (T^T E T)^-1 T^T the iteration reads, `dropped` the number of degenerate directions left out, `times` the setup's
+    synchronised wall milliseconds {"aggregation", "E", "inverse"}."""
+
+    def __init__(self, A, w, agg, agg_ptr, agg_nodes, centre, radius, rel):
+        self.A, self.device = A, A.device
+        self.w = w
+        self.agg, self.agg_ptr, self.agg_nodes = agg, agg_ptr, agg_nodes
+        self.centre, self.radius, self.rel = centre, radius, rel
+        self.n_aggregates = int(agg_ptr.numel()) - 1
+        self.m = 6 * self.n_aggregates
+        self.dropped = 0
+        self.E = self.Einv = None
+        self.times = {}
+
+    def _restrict(self, rel, w, r):
+        c = torch.empty(self.m, dtype=F64, device=self.device)
+        C.check(C.lib().fem_coarse_restrict(self.A.n_rows, self.A.bs, self.n_aggregates, C.ptr(self.agg_ptr),
+                                            C.ptr(self.agg_nodes), C.ptr(rel), C.ptr(w), C.ptr(r), C.ptr(c),
+                                            C.stream(self.device)), "fem_coarse_restrict")
+        return c
+
+    def _vec(self, v, what):
+        v = v.to(device=self.device, dtype=F64).contiguous().view(-1)
+        if v.numel() != self.A.n:
+            raise ValueError(f"CoarseSpace: {what} must hold {self.A.n} values, got {v.numel()}")
+        return v
+
+    def restrict(self, r):
+        """c [m] = Z^T r."""
+        with C.device_scope(self.device):
+            return self._restrict(self.rel, self.w, self._vec(r, "r"))
+
+    def apply(self, r, w=None):
+        """z = w o r + Z Einv Z^T r: the preconditioner as an operator. `w` defaults to the weights the space was built
+        with; another `w` must have the same zeros (they mark the rows of Z that are zero)."""
+        with C.device_scope(self.device):
+            r = self._vec(r, "r")
+            w = self.w if w is None else self._vec(w, "w")
+            c = self._restrict(self.rel, w, r)
+            y = torch.empty(self.m, dtype=F64, device=self.device)
+            z = torch.empty_like(r)
+            C.check(C.lib().fem_coarse_apply(self.A.n_rows, self.A.bs, self.n_aggregates, C.ptr(self.agg),
+                                             C.ptr(self.rel), C.ptr(w), C.ptr(self.Einv), C.ptr(c), C.ptr(r), C.ptr(y),
+                                             C.ptr(z), C.stream(self.device)), "fem_coarse_apply")
+            return z
+
+    def gram(self):
+        """[k, 6, 6] blocks Z_a^T Z_a: column q is the restriction of Z's column q of every aggregate at once (the
+        aggregates are disjoint)."""
+        N, k = self.A.n_rows, self.n_aggregates
+        x, y, z = self.rel[:, 0], self.rel[:, 1], self.rel[:, 2]
+        o, l = torch.zeros_like(x), torch.ones_like(x)
+        # columns of R_i = [I | -[rel]x]
+        colsR = [(l, o, o), (o, l, o), (o, o, l), (o, -z, y), (z, o, -x), (-y, x, o)]
+        live = (self.agg >= 0).to(F64)[:, None] * (self.w.view(N, 3) != 0).to(F64)
+        G = torch.empty((k, 6, 6), dtype=F64, device=self.device)
+        for q, col in enumerate(colsR):
+            v = (torch.stack(col, 1) * live).contiguous().view(-1)
+            G[:, :, q] = self._restrict(self.rel, self.w, v).view(k, 6)
+        return G
+
+    def galerkin(self):
+        """E [m, m] = Z^T A Z over the free rows and columns (records per row and neighbour aggregate, a stable sort by
+        key, one wave per key summing in record order)."""
+        lib, A, dev, k = C.lib(), self.A, self.device, self.n_aggregates
+        g, N, st = A.g, A.n_rows, C.stream(self.device)
+        cols, dcols = A._multi_cols()
+        vals = A.plain_values()
+        cnt = torch.empty(N, dtype=I64, device=dev)
+        C.check(lib.fem_coarse_galerkin_count(N, A.bs, C.ptr(g.slice_ptr), cols, dcols, C.ptr(self.agg), C.ptr(cnt),
+                                              st), "fem_coarse_galerkin_count")
+        off = torch.empty(N + 1, dtype=I64, device=dev)
+        work = torch.empty(int(lib.fem_scan_work_len(N)) + 1, dtype=I64, device=dev)
+        C.check(lib.fem_scan_i64(C.ptr(cnt), N, C.ptr(off), C.ptr(work), st), "fem_scan_i64")
+        nrec = int(off[N].item())
+        keys = torch.empty(max(nrec, 1), dtype=I64, device=dev)
+        rec = torch.empty((max(nrec, 1), 36), dtype=F64, device=dev)
+        C.check(lib.fem_coarse_galerkin(N, A.bs, k, C.ptr(g.slice_ptr), cols, dcols, C.ptr(vals), C.ptr(self.agg),
+                                        C.ptr(self.rel), C.ptr(self.w), C.ptr(off), C.ptr(keys), C.ptr(rec), st),
+                "fem_coarse_galerkin")
+        skeys, order = torch.sort(keys[:nrec], stable=True)
+        ukeys, counts = torch.unique_consecutive(skeys, return_counts=True)
+        key_ptr = torch.zeros(ukeys.numel() + 1, dtype=I64, device=dev)
+        key_ptr[1:] = torch.cumsum(counts, 0)
+        E = torch.zeros((self.m, self.m), dtype=F64, device=dev)
+        C.check(lib.fem_coarse_galerkin_sum(int(ukeys.numel()), k, C.ptr(ukeys), C.ptr(key_ptr),
+                                            C.ptr(order.contiguous()), C.ptr(rec), C.ptr(E), st),
+                "fem_coarse_galerkin_sum")
+        self.records = nrec
+        return E
+
+    def invert(self, E):
+        """(Einv, dropped): the 6 x 6 Gram blocks eigen-decomposed (batched, on the host: k small matrices), directions
+        below COARSE_DROP of a block's largest eigenvalue dropped and the rest kept as the orthonormal T; Einv =
+        T (T^T E T)^-1 T^T from a Cholesky on the device, symmetrised. ValueError when the Cholesky fails."""
+        k, dev = self.n_aggregates, self.device
+        lam, V = torch.linalg.eigh(self.gram().cpu())            # ascending per block
+        keep = lam > COARSE_DROP * lam[:, -1:]
+        keep[:, -1] = True
+        a_of, q_of = torch.nonzero(keep, as_tuple=True)          # kept directions, by aggregate then eigenvalue
+        mk = int(a_of.numel())
+        T = torch.zeros((self.m, mk), dtype=F64)
+        rows = (6 * a_of)[:, None] + torch.arange(6)[None, :]
+        T[rows, torch.arange(mk)[:, None]] = V[a_of, :, q_of]
+        T = T.to(dev)
+        Es = 0.5 * (E + E.T)
+        Ek = T.T @ Es @ T
+        Ek = 0.5 * (Ek + Ek.T)
+        L, info = torch.linalg.cholesky_ex(Ek)
+        info = int(info)
+        if info != 0 or not bool(torch.isfinite(L).all()):
+            bad = int(a_of[info - 1]) if info > 0 else -1
+            raise ValueError(f"rigid_coarse_space: the coarse matrix Z^T A Z is not positive definite (pivot "
+                             f"{info - 1}, aggregate {bad}); is the matrix clamped and w its Jacobi weights?")
+        Ik = torch.cholesky_solve(torch.eye(mk, dtype=F64, device=dev), L)
+        Einv = T @ (0.5 * (Ik + Ik.T)) @ T.T
+        return (0.5 * (Einv + Einv.T)).contiguous(), 6 * k - mk
+
+
 @_scoped
 class SellMatrix:
     """Assembled global operator in SELL-64 with bs x bs blocks (bs = dofs per node)."""
@@ -934,6 +1065,132 @@ class SellMatrix:
         if history:
             hist = torch.cat(hists, dim=1)[: min(max(its), max(max_iter, 1))]
         return MultiPcgResult(x, its, stts, rzs, pqs, hist)
+
+    # ---------------------------------------------------------------- two-level PCG
+    def rigid_coarse_space(self, coords, w, n_aggregates=None, aggregates=None) -> "CoarseSpace":
+        """The rigid-body coarse space of this bs = 3 matrix for M^-1 = diag(w) + Z (Z^T A Z)^-1 Z^T (pcg_two_level).
+        coords [n_rows, 3]; `w` [n] the masked Jacobi weights: dofs with w != 0 are free, a node is free if any of its
+        dofs is, rows of Z at the other dofs are zero. The aggregates are `dist.rcb_partition` of the free nodes into
+        `n_aggregates` parts (default ceil(free nodes / COARSE_TARGET), clamped to [1, COARSE_MAX_AGG]), or the
+        caller's ids `aggregates` [n_rows] (-1: none; any labels, numbered here in ascending order). Per aggregate:
+        centre and RMS radius rho of its free nodes, both rounded to fp32 (so that rel = (x - c) / rho carries the
+        same bits whatever order the sums ran in); directions a degenerate aggregate cannot carry (a 2-node aggregate
+        has no rotation about its axis) are dropped. ValueError for bs != 3, a 6-dof shell system (more rows than
+        nodes) and a coarse matrix that is not positive definite."""
+        import time
+        try:
+            from . import dist as _dist
+        except ImportError:  # pragma: no cover - flat import
+            import dist as _dist  # type: ignore
+        N, dev = self.g.n_nodes, self.device
+        if self.bs != 3:
+            raise ValueError(f"rigid_coarse_space: a bs = 3 matrix with 3 translational dofs per node is needed "
+                             f"(bs = {self.bs})")
+        coords = coords.to(device=dev, dtype=F64).contiguous()
+        if coords.dim() != 2 or tuple(coords.shape) != (N, 3):
+            raise ValueError(f"rigid_coarse_space: coords must be [{N}, 3] (one node per block row; 6-dof shell "
+                             f"systems are out of scope), got {list(coords.shape)}")
+        if w is None or w.numel() != self.n:
+            raise ValueError(f"rigid_coarse_space: w must hold {self.n} values (Jacobi weights, zero on the fixed dofs)")
+        w = w.to(device=dev, dtype=F64).contiguous().view(-1)
+
+        def tick():
+            torch.cuda.synchronize(dev)
+            return time.perf_counter()
+
+        t0 = tick()
+        free = (w.view(N, 3) != 0).any(1)
+        if aggregates is None:
+            ids = torch.nonzero(free).view(-1)
+            nfree = int(ids.numel())
+            if nfree == 0:
+                raise ValueError("rigid_coarse_space: no free dof (w is zero everywhere)")
+            k = -(-nfree // COARSE_TARGET) if n_aggregates is None else int(n_aggregates)
+            if n_aggregates is not None and not 1 <= k <= COARSE_MAX_AGG:
+                raise ValueError(f"rigid_coarse_space: 1 to {COARSE_MAX_AGG} aggregates, got {n_aggregates}")
+            k = max(1, min(k, COARSE_MAX_AGG, nfree))
+            label = torch.full((N,), -1, dtype=I64, device=dev)
+            label[ids] = _dist.rcb_partition(coords[ids], k)
+        else:
+            label = aggregates.to(device=dev, dtype=I64).view(-1).clone()
+            if label.numel() != N:
+                raise ValueError(f"rigid_coarse_space: aggregates must hold {N} ids, got {label.numel()}")
+            label[~free] = -1
+        sel = torch.nonzero(label >= 0).view(-1)
+        if sel.numel() == 0:
+            raise ValueError("rigid_coarse_space: no free node lies in an aggregate")
+        uniq, inv = torch.unique(label[sel], return_inverse=True)   # ascending labels -> 0 .. k - 1
+        k = int(uniq.numel())
+        if k > COARSE_MAX_AGG:
+            raise ValueError(f"rigid_coarse_space: {k} aggregates exceed {COARSE_MAX_AGG} (m = 6 k <= "
+                             f"{6 * COARSE_MAX_AGG})")
+        agg = torch.full((N,), -1, dtype=I32, device=dev)
+        agg[sel] = inv.to(I32)
+        order = torch.sort(inv, stable=True).indices              # grouped by aggregate, ascending inside each
+        agg_nodes = sel[order].to(I32).contiguous()
+        agg_ptr = torch.zeros(k + 1, dtype=I32, device=dev)
+        agg_ptr[1:] = torch.cumsum(torch.bincount(inv, minlength=k), 0).to(I32)
+        cs = CoarseSpace(self, w, agg, agg_ptr, agg_nodes, None, None, None)
+        # centre and radius from the restriction kernel (translation rows of Z^T with rel = 0, all dofs counted): the
+        # node list in order, a fixed tree
+        ones, zero = torch.ones(self.n, dtype=F64, device=dev), torch.zeros((N, 3), dtype=F64, device=dev)
+        cnt = (agg_ptr[1:] - agg_ptr[:-1]).to(F64)[:, None]
+        centre = (cs._restrict(zero, ones, coords.view(-1)).view(k, 6)[:, :3] / cnt).float().double()
+        live = (agg >= 0)[:, None]
+        ai = agg.long().clamp(min=0)
+        d = torch.where(live, coords - centre[ai], zero)
+        radius = (cs._restrict(zero, ones, (d * d).contiguous().view(-1)).view(k, 6)[:, :3].sum(1, keepdim=True)
+                  / cnt).sqrt().float().double()
+        radius = torch.where(radius > 0, radius, torch.ones_like(radius))   # a one-node aggregate
+        cs.centre, cs.radius = centre, radius.view(-1)
+        cs.rel = torch.where(live, d / radius[ai], zero).contiguous()
+        t1 = tick()
+        cs.E = cs.galerkin()
+        t2 = tick()
+        cs.Einv, cs.dropped = cs.invert(cs.E)
+        t3 = tick()
+        cs.times = {"aggregation": (t1 - t0) * 1e3, "E": (t2 - t1) * 1e3, "inverse": (t3 - t2) * 1e3}
+        return cs
+
+    def pcg_two_level(self, b, x0=None, w=None, coarse=None, tol=1e-8, max_iter=1000, history=False, chunk=32):
+        """PCG with the two-level preconditioner of `coarse` (rigid_coarse_space; required): z = w o r + Z Einv Z^T r,
+        MODE_PCG's semantics with this z (stop on sqrt(r.z) < tol, history of sqrt(r.z)) plus one guard, p.Ap <= 0 or
+        non-finite -> PCG_BREAKDOWN at that iteration (Einv is only numerically positive definite). `w` defaults to
+        the weights the space was built with. Plain launches (include/fem355.h fem_pcg2_*); reads the plain SELL
+        values like pcg_multi. Returns a PcgResult."""
+        if self.bs != 3:
+            raise ValueError(f"pcg_two_level: a bs = 3 matrix is needed (bs = {self.bs})")
+        if coarse is None or coarse.A is not self:
+            raise ValueError("pcg_two_level: `coarse` must be this matrix's CoarseSpace (rigid_coarse_space)")
+        lib = C.lib()
+        b = b.to(device=self.device, dtype=F64).contiguous().view(-1)
+        if b.numel() != self.n:
+            raise ValueError(f"pcg_two_level: b must hold {self.n} values, got {b.numel()}")
+        x = (torch.zeros(self.n, dtype=F64, device=self.device) if x0 is None
+             else x0.to(device=self.device, dtype=F64).clone().contiguous().view(-1))
+        w = coarse.w if w is None else w.to(device=self.device, dtype=F64).contiguous().view(-1)
+        if x.numel() != self.n or w.numel() != self.n:
+            raise ValueError(f"pcg_two_level: x0 and w must hold {self.n} values")
+        hist = torch.full((max(max_iter, 1),), float("nan"), dtype=F64, device=self.device) if history else None
+        cols, dcols = self._multi_cols()
+        h = ctypes.c_void_p()
+        C.check(lib.fem_pcg2_create(self.g.n_nodes, self.bs, C.ptr(self.g.slice_ptr), cols, dcols,
+                                    C.ptr(self.plain_values()), C.ptr(b), C.ptr(x), C.ptr(w), coarse.n_aggregates,
+                                    C.ptr(coarse.agg), C.ptr(coarse.agg_ptr), C.ptr(coarse.agg_nodes),
+                                    C.ptr(coarse.rel), C.ptr(coarse.Einv), float(tol), C.ptr(hist),
+                                    hist.numel() if hist is not None else 0, C.stream(self.device), ctypes.byref(h)),
+                "fem_pcg2_create")
+        try:
+            it, stt, rz = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+            C.check(lib.fem_pcg2_solve(h, int(max_iter), int(chunk), ctypes.byref(it), ctypes.byref(stt),
+                                       ctypes.byref(rz)), "fem_pcg2_solve")
+            sc = (ctypes.c_double * 6)()
+            C.check(lib.fem_pcg2_scalars(h, sc), "fem_pcg2_scalars")
+        finally:
+            lib.fem_pcg2_destroy(h)
+        if hist is not None:
+            hist = hist[: min(it.value, hist.numel())]
+        return PcgResult(x, it.value, stt.value, rz.value, sc[1], hist)
 
     # ---------------------------------------------------------------- stiffness and mass together
     def _mass_form(self, what, mass):

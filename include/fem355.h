@@ -795,6 +795,51 @@ int fem_mpcg_solve(fem_mpcg* s, int max_iter, int chunk, int* iters, int* status
 int fem_mpcg_scalars(fem_mpcg* s, double* out);
 void fem_mpcg_destroy(fem_mpcg* s);
 
+/* ------------------------------------------------------------------ two-level PCG (csrc/pcg_coarse.hip)
+ * The Jacobi preconditioner plus an additive coarse correction over aggregates of nodes, each carrying its six
+ * rigid-body modes: M^-1 = diag(w) + Z (Z^T A Z)^-1 Z^T. bs must be 3 with three translational dofs per node
+ * (anything else, a 6-dof shell system included, is FEM_EARG), k is 1 to FEM_COARSE_MAX_AGG aggregates, m = 6 k. Z is
+ * never stored: the row block of node i is R_i = [I_3 | -[rel_i]x] with rel [nrows, 3] the node's position relative to
+ * the centre of its aggregate agg [nrows] (int32, -1: in no aggregate); the rows of the dofs with w == 0 are zero.
+ * agg_ptr [k + 1] / agg_nodes list every aggregate's nodes, ascending inside an aggregate. The matrix arguments are
+ * those of fem_mpcg_create. Plain launches, no floating-point atomics, every sum in an order fixed by the sizes alone
+ * (the same bits on every run), rows >= nrows never read or stored.
+ * fem_coarse_restrict: c [m] = Z^T r, one workgroup per aggregate, the node list in order.
+ * fem_coarse_apply: z = w o r + Z (Einv c) for the dense symmetric Einv [m, m]; y [m] receives Einv c.
+ * fem_coarse_galerkin_count / fem_coarse_galerkin / fem_coarse_galerkin_sum: E = Z^T A Z as records. count [nrows]
+ *   (int64) = the distinct aggregates among a row's neighbours (0 for a row in none); offset [nrows + 1] its exclusive
+ *   scan (fem_scan_i64); every row then writes one record per neighbour aggregate b in ascending id: keys [.] =
+ *   agg[row] k + b and rec [., 36] = R_i^T sum_{j in b} A_ij R_j. The caller sorts the keys (stable) into `order`;
+ *   the sum adds the records of each of the nkeys distinct keys ukeys (records order[key_ptr[u] .. key_ptr[u + 1]))
+ *   in that order into the zero-initialised E [m, m]. */
+#define FEM_COARSE_MAX_AGG 512
+int fem_coarse_restrict(int64_t nrows, int bs, int k, const int32_t* agg_ptr, const int32_t* agg_nodes,
+                        const double* rel, const double* w, const double* r, double* c, fem_stream_t stream);
+int fem_coarse_apply(int64_t nrows, int bs, int k, const int32_t* agg, const double* rel, const double* w,
+                     const double* Einv, const double* c, const double* r, double* y, double* z, fem_stream_t stream);
+int fem_coarse_galerkin_count(int64_t nrows, int bs, const int64_t* slice_ptr, const int32_t* cols,
+                              const int16_t* dcols, const int32_t* agg, int64_t* count, fem_stream_t stream);
+int fem_coarse_galerkin(int64_t nrows, int bs, int k, const int64_t* slice_ptr, const int32_t* cols,
+                        const int16_t* dcols, const double* vals, const int32_t* agg, const double* rel,
+                        const double* w, const int64_t* offset, int64_t* keys, double* rec, fem_stream_t stream);
+int fem_coarse_galerkin_sum(int64_t nkeys, int k, const int64_t* ukeys, const int64_t* key_ptr, const int64_t* order,
+                            const double* rec, double* E, fem_stream_t stream);
+/* The lock-step context in the shape of fem_mpcg_* at one column, FEM_MODE_PCG's semantics with the two-level z: stop
+ * on sqrt(r.z) < tol, hist [hist_len] (may be NULL) receives sqrt(r.z) per iteration. One guard more than
+ * FEM_MODE_PCG, because Einv is only numerically positive definite: p.q <= 0 or non-finite stops with
+ * FEM_PCG_BREAKDOWN at that iteration. x holds the start vector on entry and the solution on exit. */
+typedef struct fem_pcg2 fem_pcg2;
+int fem_pcg2_create(int64_t nrows, int bs, const int64_t* slice_ptr, const int32_t* cols, const int16_t* dcols,
+                    const double* vals, const double* b, double* x, const double* w, int k, const int32_t* agg,
+                    const int32_t* agg_ptr, const int32_t* agg_nodes, const double* rel, const double* Einv, double tol,
+                    double* hist, int64_t hist_len, fem_stream_t stream, fem_pcg2** out);
+/* [sync] run from the x in place; the host enqueues `chunk` iterations at a time and reads the state in between;
+ * iterations after a stop are no-ops on the device */
+int fem_pcg2_solve(fem_pcg2* s, int max_iter, int chunk, int* iters, int* status, double* rz);
+/* [sync] fem_pcg_scalars' six values */
+int fem_pcg2_scalars(fem_pcg2* s, double* out6);
+void fem_pcg2_destroy(fem_pcg2* s);
+
 /* ------------------------------------------------------------------ modal analysis (csrc/modal.hip)
  * The tall-skinny kernels of the block LOBPCG that SellMatrix.eig_lowest drives for the lowest eigenpairs of
  * K u = lambda M u. Multi-vectors are [n, nv] row-major as above (nv 2, 4 or 8; 16-byte aligned). Plain launches;
