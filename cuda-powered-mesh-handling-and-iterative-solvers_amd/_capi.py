@@ -36,6 +36,7 @@ MASS_SELL, MASS_DIAG = 0, 1   # include/fem355.h fem_mass_form
 MAT_SVK, MAT_NEO_HOOKEAN = 0, 1   # include/fem355.h FEM_MAT_*
 MATERIALS = {"svk": MAT_SVK, "neo_hookean": MAT_NEO_HOOKEAN}
 SHELL_LOCAL, SHELL_POINTS, SHELL_GLOBAL = 0, 1, 2   # include/fem355.h FEM_SHELL_*
+LOAD_NONE, LOAD_UNIFORM, LOAD_NODAL, LOAD_ELEMENT = 0, 1, 2, 3   # include/fem355.h FEM_LOAD_*
 MODAL_OUT_GM, MODAL_OUT_NORMS, MODAL_OUT_LEN = 576, 1152, 1168   # include/fem355.h FEM_MODAL_OUT_*
 
 _P = ctypes.c_void_p
@@ -220,6 +221,11 @@ SIGNATURES = {
     "fem_shell_geom": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fem_shell_apply": (_I, [_P, _P, _P, _I, _P, _P, _L, _P, _P, _P]),
     "fem_shell_stress": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P]),
+    "fem_tet4_loads": (_I, [_P, _P, _L, _P, _P, _L, _D, _P, _I, _D, _D, _D, _P, _I, _D, _P, _P, _P, _P]),
+    "fem_iso_loads": (_I, [_P, _P, _L, _I, _P, _P, _P, _I, _I, _D, _P, _I, _D, _D, _D, _P, _I, _D, _P, _P]),
+    "fem_face_loads": (_I, [_P, _P, _L, _I, _P, _P, _I, _P, _I, _P, _P]),
+    "fem_tet4_stress_thermal": (_I, [_P, _P, _L, _P, _D, _D, _D, _P, _I, _D, _P, _P, _P, _P]),
+    "fem_iso_stress_thermal": (_I, [_P, _P, _L, _I, _P, _D, _D, _D, _P, _I, _D, _P, _P, _P, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -24,6 +24,7 @@ try:
     from .shell import shell_global_K
     from .constraints import *  # noqa: F401,F403
     from .constraints import ConstraintSet
+    from .loads import *  # noqa: F401,F403  (distributed loads, re-exported like the element API)
 except ImportError:  # pragma: no cover - flat import from the package directory
     import _capi as C  # type: ignore
     import system as _sys  # type: ignore
@@ -34,6 +35,7 @@ except ImportError:  # pragma: no cover - flat import from the package directory
     from shell import shell_global_K  # type: ignore
     from constraints import *  # type: ignore # noqa
     from constraints import ConstraintSet  # type: ignore
+    from loads import *  # type: ignore # noqa
 
 from collections import OrderedDict
 

@@ -978,6 +978,53 @@ int fem_shell_apply(const double* Ke, const double* unit, const int64_t* conn, i
 int fem_shell_stress(const double* coords, const int64_t* conn, int64_t M, int npe, const double* D6,
                      const double* pts, const double* u, double* nmq, int64_t* bad_idx, fem_stream_t stream);
 
+/* ------------------------------------------------------------------ distributed loads (csrc/loads.hip)
+ * Physical loads turned into nodal forces, and the stress recovery that takes the thermal strain off. No reference
+ * function exists (its solvers take a finished force array): parity unpinned. All fp64; every nodal sum runs over the
+ * node -> element incidence in ascending order (no atomics, the same bits on every run, zero rows for nodes without
+ * elements). How an optional array is read is given by a FEM_LOAD_* mode:
+ *     FEM_LOAD_NONE absent (NULL) | FEM_LOAD_UNIFORM one value ([1], an acceleration or traction [3]) |
+ *     FEM_LOAD_NODAL one row per node | FEM_LOAD_ELEMENT one row per element (T) or per face (p, t)
+ * All such arrays are device memory. beta = alpha (D00 + 2 D01) with the isotropic D of `solver/element.py:282-306`.
+ * fem_tet4_loads: F [N,3], per node the sum over its incident tets of
+ *     body     rho V/4 g (uniform) or rho V/20 (a_a + sum_b a_b) (nodal), V = |det|/6 as the consistent mass;
+ *     thermal  V beta dT_e grad N_a = V B_a^T D (alpha dT_e m), m = (1,1,1,0,0,0), gradients and V those of
+ *              fem_tet4_ke (a uniform dT gives K_e times the expansion field alpha dT x); dT_e = mean of the four
+ *              nodal T - T_ref (nodal), T[e] - T_ref (element) or T[0] - T_ref (uniform).
+ *   fe == NULL: one node-centred pass that recomputes each incident tet's geometry; fe [M,4,3] given: the two-pass
+ *   form (element vectors, then fem_tet4_nl_gather). bad_idx as fem_tet4_ke (nullable, preset to M). M == 0: F = 0.
+ * fem_iso_loads: element vectors fe [M,npe,3] of c3d8 / c3d6 / c3d10 (npe 8 / 6 / 10) from shape values Nv
+ *   [n_ip,npe], natural derivatives dN [n_ip,npe,3] and weights w [n_ip] (n_ip <= 32); the caller gathers them with
+ *   fem_tet4_nl_gather.
+ *     body     rho sum_q w_q |detJ_q| N_a(q) a(q), a(q) uniform or interpolated with Nv;
+ *     thermal  sum_q c_q beta dT(q) grad N_a(q), c_q = w_q detJ_q (signed, FEM_ISO_SUM) or the wedge volume at the
+ *              single point (FEM_ISO_VOLUME, npe 6, n_ip 1) -- fem_iso_ke's factors; dT(q) interpolated with Nv.
+ * fem_face_loads: face vectors fv [F,nf,3] of tri3 / quad4 faces (nf 3 / 4) under a pressure p (against the normal) or
+ *   a traction t [3] (exactly one, FEM_LOAD_UNIFORM or FEM_LOAD_ELEMENT): tri3 -(p/3) (A n) or (A/3) t per node; quad4
+ *   2x2 Gauss on n dA = x_xi x x_eta. The normal is the right-hand normal of the node order, flipped when it points
+ *   from the face centroid towards node extra[f] (extra nullable). A face with a repeated node or zero area gives zeros.
+ * fem_tet4_stress_thermal / fem_iso_stress_thermal: fem_tet4_stress / fem_iso_stress (layouts 0 and 1, npe 6 / 8) with
+ *   sigma = D (B u_e - alpha dT m) and von Mises of that tensor; dT as the loads above (Nv [n_ip,npe] interpolates it
+ *   at the points). */
+enum { FEM_LOAD_NONE = 0, FEM_LOAD_UNIFORM = 1, FEM_LOAD_NODAL = 2, FEM_LOAD_ELEMENT = 3 };
+int fem_tet4_loads(const double* coords, const int64_t* conn, int64_t M, const int32_t* inc_ptr, const int32_t* inc,
+                   int64_t N, double rho, const double* accel, int accel_mode, double E, double nu, double alpha,
+                   const double* T, int t_mode, double T_ref, double* fe, double* F, int64_t* bad_idx,
+                   fem_stream_t stream);
+int fem_iso_loads(const double* coords, const int64_t* conn, int64_t M, int npe, const double* Nv, const double* dN,
+                  const double* w, int n_ip, int mode, double rho, const double* accel, int accel_mode, double E,
+                  double nu, double alpha, const double* T, int t_mode, double T_ref, double* fe,
+                  fem_stream_t stream);
+int fem_face_loads(const double* coords, const int64_t* faces, int64_t F, int nf, const int64_t* extra,
+                   const double* p, int p_mode, const double* t, int t_mode, double* fv, fem_stream_t stream);
+int fem_tet4_stress_thermal(const double* coords, const int64_t* conn, int64_t M, const double* u, double E, double nu,
+                            double alpha, const double* T, int t_mode, double T_ref, double* sig, double* vm,
+                            int64_t* bad_idx, fem_stream_t stream);
+int fem_iso_stress_thermal(const double* coords, const int64_t* conn, int64_t M, int npe, const double* u, double E,
+                           double nu, double alpha, const double* T, int t_mode, double T_ref, const double* Nv,
+                           const double* dN, const double* w, int n_ip, int layout, double* sig, double* vm,
+                           fem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
