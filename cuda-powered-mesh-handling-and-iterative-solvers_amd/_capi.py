@@ -226,6 +226,7 @@ SIGNATURES = {
     "fem_face_loads": (_I, [_P, _P, _L, _I, _P, _P, _I, _P, _I, _P, _P]),
     "fem_tet4_stress_thermal": (_I, [_P, _P, _L, _P, _D, _D, _D, _P, _I, _D, _P, _P, _P, _P]),
     "fem_iso_stress_thermal": (_I, [_P, _P, _L, _I, _P, _D, _D, _D, _P, _I, _D, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "fem_geo_scalar": (_I, [_P, _P, _L, _I, _P, _D, _D, _P, _P, _P, _I, _P, _P, _P]),
 }
 
 _lib = None

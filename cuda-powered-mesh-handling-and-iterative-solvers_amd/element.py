@@ -916,6 +916,87 @@ def compute_c3d4_deformation_gradient(coords, elements, displacement, device="cu
     return _out(Fm, device, dtype), _out(det, device, dtype)
 
 
+# ============================================================================ geometric stiffness (csrc/buckling.hip)
+# K_g(sigma) of a linear prestress for c3d4 / c3d6 / c3d8 / c3d10: the matrix of linear buckling (K + lambda K_g) phi = 0
+# and of stress-stiffened modes. The reference has neither.
+_GEO_NPE = {"c3d4": 4, "c3d6": 6, "c3d8": 8, "c3d10": 10}
+_DN_C3D4 = [[-1.0, -1.0, -1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
+
+
+def geometric_integration_points(element_type, dtype=F64):
+    """Quadrature of the geometric stiffness -> (natural derivatives dN [n, npe, 3], weights [n]) on the host: c3d4 one
+    point, weight 1/6, with the P1 derivatives (row a is the vertex function of node a: N_0 = 1 - xi - eta - zeta,
+    N_1 = xi, N_2 = eta, N_3 = zeta); c3d8 / c3d6 / c3d10 the rules of mass_integration_points (the 14-point c3d10 rule
+    is exact for the cubic integrand grad N_a . sigma grad N_b of an affine element under a linear stress)."""
+    et = element_type.lower()
+    if et == "c3d4":
+        return torch.tensor([_DN_C3D4], dtype=dtype), torch.tensor([1.0 / 6.0], dtype=dtype)
+    if et in _N:
+        p, w = mass_integration_points(et)
+        fn = _ISO[et][1]
+        dN = torch.tensor([fn(*[float(v) for v in p[q]]) for q in range(p.shape[0])], dtype=dtype)
+        return dN, w.to(dtype)
+    _unsupported(element_type)
+
+
+def _check_geometric(coords, elements, element_type, displacement, E, nu, prestress):
+    """Argument checks of compute_geometric_stiffness -- ValueError before any device call. Returns the type name."""
+    et = element_type.lower() if isinstance(element_type, str) else element_type
+    if et not in _GEO_NPE:
+        _unsupported(element_type)
+    npe = _GEO_NPE[et]
+    if coords.dim() != 2 or coords.shape[1] != 3:
+        raise ValueError(f"coords must be [N, 3], got {list(coords.shape)}")
+    if elements.dim() != 2 or elements.shape[1] != npe:
+        raise ValueError(f"{et} expects {npe} nodes per element, got {list(elements.shape)}")
+    if displacement is None and prestress is None:
+        raise ValueError("compute_geometric_stiffness: a displacement, a prestress or both are needed")
+    if displacement is not None:
+        if E is None or nu is None:
+            raise ValueError("compute_geometric_stiffness: E and nu are needed with a displacement")
+        if tuple(displacement.shape) != (coords.shape[0], 3):
+            raise ValueError(f"displacement must be [N, 3] with N = {coords.shape[0]} nodes, got "
+                             f"{list(displacement.shape)}")
+    if prestress is not None and tuple(prestress.shape) != (elements.shape[0], 3, 3):
+        raise ValueError(f"prestress must be [M, 3, 3] with M = {elements.shape[0]} elements, got "
+                         f"{list(prestress.shape)}")
+    return et
+
+
+def compute_geometric_stiffness(coords, elements, element_type, displacement=None, E=None, nu=None, prestress=None,
+                                device="cuda:0", dtype=torch.float32, scalar=True):
+    """Geometric (initial-stress) stiffness of c3d4 / c3d6 / c3d8 / c3d10 elements under a linear prestress:
+    K_g,e = Gs_e (x) I3, Gs_e[a][b] = sum_q w_q |detJ_q| grad N_a^T sigma_q grad N_b (geometric_integration_points).
+    sigma_q = D(E, nu) B_q u_e at every point when `displacement` [N, 3] is given (E and nu are then required), plus
+    the per-element constant `prestress` [M, 3, 3] when given (upper triangle read: what compute_element_stress /
+    compute_thermal_element_stress return); at least one of the two. scalar=True returns the factor Gs [M, npe, npe]
+    -- assembled as a bs = 1 matrix on the node pattern it takes every `mass` argument of system.SellMatrix
+    (matvec_km_multi, scaled_add_mass, quadforms, buckling_lowest); scalar=False the full [M, 3 npe, 3 npe] for
+    functions that take element matrices (compute_nodal_forces, the solvers). Symmetric bit for bit; rows sum to zero
+    up to rounding. ValueError for another element type, missing or misshapen inputs (before any device call) and for
+    a degenerate element (detJ = 0 or not finite at a point)."""
+    et = _check_geometric(coords, elements, element_type, displacement, E, nu, prestress)
+    lib = C.lib()
+    dev, coords, elements = _prep(coords, elements, device)
+    M, npe = elements.shape
+    u = None if displacement is None else _disp(displacement, dev, coords.shape[0])
+    s0 = None if prestress is None else prestress.to(device=dev, dtype=F64).contiguous()
+    dN = _dev_const((et, "geo-dN"), lambda: geometric_integration_points(et)[0], dev)
+    w = _dev_const((et, "geo-w"), lambda: geometric_integration_points(et)[1], dev)
+    Gs = torch.empty((M, npe, npe), dtype=F64, device=dev)
+    bad = torch.zeros(M, dtype=torch.uint8, device=dev)
+    C.check(lib.fem_geo_scalar(C.ptr(coords), C.ptr(elements), M, npe, C.ptr(u), float(E if u is not None else 0.0),
+                               float(nu if u is not None else 0.0), C.ptr(s0), C.ptr(dN), C.ptr(w), dN.shape[0],
+                               C.ptr(Gs), C.ptr(bad), C.stream(dev)), "fem_geo_scalar")
+    if M and bool(bad.any()):
+        raise ValueError("Singular matrix encountered while computing B matrix.")
+    if not scalar:
+        Gs = torch.kron(Gs, torch.eye(3, dtype=F64, device=dev).view(1, 3, 3))
+    return _out(Gs, device, dtype)
+
+
+__all__ += ["geometric_integration_points", "compute_geometric_stiffness"]
+
 __all__ += [
     "compute_c3d4_tangent_K_matrix", "compute_c3d4_internal_forces", "compute_c3d4_strain_energy",
     "compute_c3d4_cauchy_stress", "compute_c3d4_deformation_gradient",

@@ -623,8 +623,21 @@ def modal_solver(K, M, elements, fixed, num_nodes, num_modes=6, tol=1e-8, max_it
     from which the factor M[:, ::dpn, ::dpn] is taken. Both matrices are assembled on one cached graph. Returns
     (freq_hz = sqrt(lam) / 2 pi [num_modes], lam [num_modes], modes [num_modes, N, dpn]) in `dtype` and prints one
     line per mode; with return_info also the ModalResult."""
-    what = "modal_solver"
+    return _modal_solve("modal_solver", K, M, elements, fixed, num_nodes, num_modes, tol, max_iter, block, seed, device,
+                        dtype, return_info)
+
+
+def _modal_solve(what, K, M, elements, fixed, num_nodes, num_modes, tol, max_iter, block, seed, device, dtype,
+                 return_info, Gs=None, load_factor=0.0):
+    """modal_solver; with Gs [Me, npe, npe] on K + load_factor K_g (stress_stiffened_modal_solver)."""
     dpn = _check_modal(what, K, M, elements, num_nodes, num_modes, lambda d: (1, d))
+    if Gs is not None:
+        npe = elements.shape[1]
+        if dpn != 3:
+            raise ValueError(f"{what}: 3 dofs per node needed, got {dpn}")
+        if not torch.is_tensor(Gs) or tuple(Gs.shape) != (elements.shape[0], npe, npe):
+            shape = list(Gs.shape) if torch.is_tensor(Gs) else type(Gs).__name__
+            raise ValueError(f"{what}: Gs must be the scalar factor [{elements.shape[0]}, {npe}, {npe}], got {shape}")
     ids = _fixed_ids(what, fixed, num_nodes)
     _sys.modal_block(num_modes, block)
     dev = _dev(device)
@@ -642,6 +655,9 @@ def modal_solver(K, M, elements, fixed, num_nodes, num_modes=6, tol=1e-8, max_it
     else:
         A.add_element_matrices(Ke, el)
         Mg.add_element_matrices(Ms, el)
+    if Gs is not None:   # K + load_factor K_g, K_g = G (x) I3 with G assembled like the scalar mass
+        Gg = _sys.SellMatrix(g, 1).add_element_matrices(Gs.to(device=dev, dtype=F64).contiguous(), el)
+        A = A.scaled_add_mass(Gg, 1.0, float(load_factor))
     res = A.eig_lowest(Mg, int(num_modes), _jacobi_weights(A, ids, dev), block=block, tol=tol, max_iter=max_iter,
                        seed=seed)
     if res.status == C.PCG_MAXITER:
@@ -656,6 +672,172 @@ def modal_solver(K, M, elements, fixed, num_nodes, num_modes=6, tol=1e-8, max_it
     modes = res.X.T.reshape(int(num_modes), num_nodes, dpn)
     ret = (freq.to(device=out, dtype=dtype), res.lam.to(device=out, dtype=dtype), modes.to(device=out, dtype=dtype))
     return ret + (res,) if return_info else ret
+
+
+# ============================================================================ linear buckling
+# The reference has no stability analysis. Linear (eigenvalue) buckling of the solid elements: the reference state
+# K u_ref = F (or a given prestress), its geometric stiffness K_g = G (x) I3 from csrc/buckling.hip, and the load factors
+# lambda of (K + lambda K_g) phi = 0 by SellMatrix.buckling_lowest (DESIGN §8r).
+_BUCKLING_NPE = {"c3d4": 4, "c3d6": 6, "c3d8": 8, "c3d10": 10}
+_CENTROID = {"c3d8": (0.0, 0.0, 0.0), "c3d6": (1.0 / 3.0, 1.0 / 3.0, 0.0), "c3d10": (0.25, 0.25, 0.25)}
+
+
+def _buckling_families(what, elements, element_type):
+    """[(type, connectivity)] of `elements` / `element_type` (one family, or a dict {type: connectivity})."""
+    if isinstance(elements, dict):
+        fams = [(str(t).lower(), el) for t, el in elements.items()]
+    elif isinstance(element_type, dict):
+        fams = [(str(t).lower(), el) for t, el in element_type.items()]
+    else:
+        fams = [(str(element_type).lower(), elements)]
+    if not fams:
+        raise ValueError(f"{what}: no element family given")
+    for et, el in fams:
+        if et not in _BUCKLING_NPE:
+            raise ValueError(f"Unsupported element type: {et}")
+        if not torch.is_tensor(el) or el.dim() != 2 or el.shape[1] != _BUCKLING_NPE[et] or el.shape[0] < 1:
+            shape = list(el.shape) if torch.is_tensor(el) else type(el).__name__
+            raise ValueError(f"{what}: {et} connectivity must be [M, {_BUCKLING_NPE[et]}] with M >= 1, got {shape}")
+    return fams
+
+
+def _check_buckling(what, coords, fams, F, fixed, E, nu, k, prestress, u_ref, tol, max_iter, linear_tol,
+                    linear_max_iter, block):
+    """ValueError for arguments that do not fit -- before any device call. Returns the fixed node ids."""
+    if not torch.is_tensor(coords) or coords.dim() != 2 or coords.shape[1] != 3:
+        raise ValueError(f"{what}: coords must be [N, 3]")
+    N = coords.shape[0]
+    if max(_max_node(el) for _, el in fams) > N:
+        raise ValueError(f"{what}: the mesh references a node outside the {N} coordinates")
+    if F is None and prestress is None and u_ref is None:
+        raise ValueError(f"{what}: a load F, a reference displacement u_ref or a prestress is needed")
+    if F is not None and tuple(F.shape) != (N, 3):
+        raise ValueError(f"{what}: F must be [{N}, 3], got {list(F.shape)}")
+    if u_ref is not None and tuple(u_ref.shape) != (N, 3):
+        raise ValueError(f"{what}: u_ref must be [{N}, 3], got {list(u_ref.shape)}")
+    if prestress is not None:
+        ps = prestress if isinstance(prestress, dict) else {fams[0][0]: prestress}
+        if len(fams) > 1 and not isinstance(prestress, dict):
+            raise ValueError(f"{what}: a mixed mesh takes prestress as a dict {{type: [M, 3, 3]}}")
+        for et, el in fams:
+            p = ps.get(et)
+            if p is not None and tuple(p.shape) != (el.shape[0], 3, 3):
+                raise ValueError(f"{what}: prestress of {et} must be [{el.shape[0]}, 3, 3], got {list(p.shape)}")
+        if set(ps) - {et for et, _ in fams}:
+            raise ValueError(f"{what}: prestress for a family that is not in the mesh: {sorted(set(ps))}")
+    if not (float(E) > 0.0 and -1.0 < float(nu) < 0.5):
+        raise ValueError(f"{what}: E > 0 and -1 < nu < 0.5 needed, got E = {E}, nu = {nu}")
+    _sys.modal_block(k, block)
+    if not (tol > 0 and linear_tol > 0 and int(max_iter) >= 0 and int(linear_max_iter) >= 1):
+        raise ValueError(f"{what}: tol, linear_tol > 0, max_iter >= 0 and linear_max_iter >= 1 needed")
+    ids = _fixed_ids(what, fixed, N)
+    if ids.numel() == 0:
+        raise ValueError(f"{what}: at least one fixed node is needed (K must be positive definite)")
+    return ids
+
+
+def _buckling_ke(coords, el, et, E, nu, dev):
+    """Stiffness [M, 3 npe, 3 npe] of one solid family for the buckling pencil, integrated with |detJ| over a rule
+    whose weights sum to the reference element's volume: c3d4 closed form, c3d8 the 2x2x2 rule, c3d6 / c3d10 the rules
+    of mass_integration_points (the reference's own c3d6 / c3d10 stiffness rules sum to 2 and 0.45, Q3 / Q2, and its
+    signed detJ makes K negative on VTK-positive quadratic tets: neither gives a physical load factor)."""
+    if et == "c3d4":
+        return compute_c3d4_K_matrix(coords, el, E, nu, device=dev, dtype=F64)
+    if et == "c3d8":
+        Ke = compute_c3d8_K_matrix(coords, el, E, nu, device=dev, dtype=F64)
+    else:
+        p, w = mass_integration_points(et)
+        ip = torch.cat([p, w[:, None]], dim=1)
+        fn = compute_c3d6_K_matrix if et == "c3d6" else compute_c3d10_K_matrix
+        Ke = fn(coords, el, E, nu, integral_point=ip, single=(et == "c3d10"), device=dev, dtype=F64)
+    J = compute_Jacobian(coords, el, et, torch.tensor(_CENTROID[et], dtype=F64), device=dev).to(F64)
+    return Ke * torch.sign(torch.linalg.det(J)).view(-1, 1, 1)
+
+
+def linear_buckling_solver(coords, elements, element_type, F, fixed, E, nu, num_modes=4, prestress=None, u_ref=None,
+                           tol=1e-8, max_iter=200, linear_tol=1e-10, linear_max_iter=10000, block=None, seed=0,
+                           device="cuda:0", dtype=torch.float64, return_info=False):
+    """Linear (eigenvalue) buckling of a solid mesh with the nodes `fixed` clamped: the `num_modes` load factors lambda
+    of smallest magnitude by which the reference load may be scaled before (K + lambda K_g) phi = 0 has a solution, and
+    their shapes. The reference state is K u_ref = F [N, 3] by Jacobi-PCG (to `linear_tol` relative, `linear_max_iter`),
+    or `u_ref` [N, 3] when supplied; `prestress` [M, 3, 3] (per-element stress, e.g. of compute_thermal_element_stress)
+    is added to its stress, and with F = None and no u_ref it is the whole reference state. `elements` is one
+    connectivity with `element_type` in c3d4 / c3d6 / c3d8 / c3d10, or a dict {type: connectivity} of a mixed mesh
+    (`prestress` then a dict too); every family adds into the same K and G. A negative factor means the load buckles
+    the structure when reversed. Returns (load_factors [num_modes] signed, ascending in magnitude, modes
+    [num_modes, N, 3] K-orthonormal, u_ref [N, 3]) in `dtype` and prints one line per mode; with return_info also the
+    BucklingResult. Never raises on non-convergence: one line tells the outer cap from a failed inner solve, and a
+    state without prestress (G = 0) is reported as a breakdown."""
+    what = "linear_buckling_solver"
+    fams = _buckling_families(what, elements, element_type)
+    ids = _check_buckling(what, coords, fams, F, fixed, E, nu, num_modes, prestress, u_ref, tol, max_iter, linear_tol,
+                          linear_max_iter, block)
+    dev = _dev(device)
+    coords = coords.to(device=dev, dtype=F64).contiguous()
+    N = coords.shape[0]
+    fams = [(et, el.to(device=dev, dtype=LONG).contiguous()) for et, el in fams]
+    if len(fams) == 1:
+        g = cached_graph(fams[0][1], N)
+    else:
+        g = _sys.build_graph(_sys.pad_connectivity([el for _, el in fams], max(el.shape[1] for _, el in fams)), N)
+    incs = [None if len(fams) == 1 else _sys.incidence(el, N) for _, el in fams]
+    A, G = _sys.SellMatrix(g, 3), _sys.SellMatrix(g, 1)
+    for (et, el), inc in zip(fams, incs):
+        A.add_element_matrices(_buckling_ke(coords, el, et, E, nu, dev), el, inc=inc)
+    w = _jacobi_weights(A, ids, dev)
+    if u_ref is not None:
+        u = u_ref.to(device=dev, dtype=F64).contiguous()
+    elif F is not None:
+        b = (F.to(device=dev, dtype=F64) * (w.view(N, 3) != 0)).reshape(-1).contiguous()
+        scale = float(torch.sqrt(torch.dot(b, w * b)))
+        if scale > 0.0:
+            res0 = A.pcg(b, None, w=w, mode=C.MODE_PCG, tol=float(linear_tol) * scale, max_iter=int(linear_max_iter))
+            if res0.status != C.PCG_CONVERGED:
+                print(f"Buckling solver: the reference solve did not converge in {linear_max_iter} iterations")
+            u = res0.x.view(N, 3)
+        else:   # no load on a free dof: the reference state is zero
+            u = torch.zeros((N, 3), dtype=F64, device=dev)
+    else:
+        u = None
+    ps = {} if prestress is None else (prestress if isinstance(prestress, dict) else {fams[0][0]: prestress})
+    for (et, el), inc in zip(fams, incs):
+        Gs = compute_geometric_stiffness(coords, el, et, displacement=u, E=E, nu=nu, prestress=ps.get(et), device=dev,
+                                         dtype=F64) if (u is not None or ps.get(et) is not None) else \
+            torch.zeros((el.shape[0], el.shape[1], el.shape[1]), dtype=F64, device=dev)
+        G.add_element_matrices(Gs, el, inc=inc)
+    res = A.buckling_lowest(G, int(num_modes), w, block=block, tol=tol, max_iter=max_iter, linear_tol=linear_tol,
+                            linear_max_iter=linear_max_iter, seed=seed)
+    if res.status == C.PCG_MAXITER and res.inner_failed:
+        print(f"Buckling solver: an inner solve did not converge in {linear_max_iter} iterations "
+              f"(outer iteration {res.iterations + 1})")
+    elif res.status == C.PCG_MAXITER:
+        print(f"Buckling solver: reached max_iter ({max_iter}) with residual {float(res.residuals.max()):.3e}")
+    elif res.status == C.PCG_BREAKDOWN:
+        print(f"Buckling solver: breakdown at iteration {res.iterations} (no prestress, or K is not positive definite "
+              "on the free dofs)")
+    for j in range(int(num_modes)):
+        print(f"Mode {j + 1}: load factor = {float(res.factors[j]):.6e}, theta = {float(res.theta[j]):.6e}, "
+              f"residual {float(res.residuals[j]):.3e}")
+    out = torch.device(device)
+    modes = res.X.T.reshape(int(num_modes), N, 3)
+    u_out = torch.zeros((N, 3), dtype=F64, device=dev) if u is None else u
+    ret = (res.factors.to(device=out, dtype=dtype), modes.to(device=out, dtype=dtype),
+           u_out.to(device=out, dtype=dtype))
+    return ret + (res,) if return_info else ret
+
+
+def stress_stiffened_modal_solver(K, M, Gs, elements, fixed, num_nodes, load_factor=1.0, num_modes=6, tol=1e-8,
+                                  max_iter=2000, block=None, seed=0, device="cuda:0", dtype=torch.float64,
+                                  return_info=False):
+    """Natural frequencies of a prestressed structure: modal_solver on K + load_factor K_g in the place of K, with
+    Gs [Me, npe, npe] the scalar factor of the geometric stiffness at the reference load
+    (compute_geometric_stiffness(..., scalar=True)); K [Me, 3 npe, 3 npe], M, elements, fixed, num_nodes and the keyword
+    arguments as modal_solver's, same returns and prints. The effective stiffness is
+    SellMatrix.scaled_add_mass(G, 1, load_factor): no kernel of its own. Compression softens: the frequencies go to zero
+    as `load_factor` approaches the first buckling factor of linear_buckling_solver (beyond it K + load_factor K_g is
+    indefinite and the solve reports a breakdown); tension stiffens."""
+    return _modal_solve("stress_stiffened_modal_solver", K, M, elements, fixed, num_nodes, num_modes, tol, max_iter,
+                        block, seed, device, dtype, return_info, Gs=Gs, load_factor=load_factor)
 
 
 # ============================================================================ transient dynamics

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import time
 from dataclasses import dataclass
 
 import torch
@@ -133,6 +134,21 @@ class ModalResult:
     residuals: torch.Tensor        # [k] ||K x - lam M x|| / (lam ||M x||) over the free dofs, as last measured
     restarts: int = 0              # iterations whose Rayleigh-Ritz dropped P
     history: torch.Tensor = None   # [iterations, k]: the residuals after every iteration
+
+
+@dataclass
+class BucklingResult:
+    """SellMatrix.buckling_lowest: the k pairs of largest |theta| of G phi = theta K phi on the free dofs, i.e. the k
+    load factors lambda = -1 / theta of smallest magnitude of (K + lambda K_g) phi = 0."""
+    factors: torch.Tensor          # [k] signed lambda, ascending in |lambda| (host, fp64)
+    theta: torch.Tensor            # [k] the Ritz values, descending in |theta| (host, fp64)
+    X: torch.Tensor                # [n, k] K-orthonormal, zeros on the fixed dofs (device)
+    iterations: int                # outer iterations (block solves with K) made
+    linear_iterations: int         # the inner PCG iterations, summed over the solves (per solve: the slowest column)
+    status: int                    # _capi.PCG_CONVERGED / PCG_MAXITER / PCG_BREAKDOWN
+    residuals: torch.Tensor        # [k] ||G x - theta K x|| / (|theta| ||K x||) over the free dofs, as last measured
+    history: torch.Tensor = None   # [iterations + 1, k]: the residuals of the start block and after every iteration
+    inner_failed: bool = False     # PCG_MAXITER because an inner solve did not converge (not the outer cap)
 
 
 # Rayleigh-Ritz guards of the block LOBPCG. MODAL_COND: the scaled Gram matrix of the mass is dropped to [X W] past
@@ -1358,6 +1374,148 @@ class SellMatrix:
             rotate(a, theta, Cm)
             has_p = True
         return result(theta, status, it, rel, restarts, hist)
+
+    def buckling_lowest(self, G, k, w, block=None, tol=1e-8, max_iter=200, linear_tol=1e-10, linear_max_iter=10000,
+                        seed=0, history=False, timers=None):
+        """The k load factors of smallest magnitude of linear buckling, (K + lambda K_g) phi = 0, with this matrix the
+        bs = 3 stiffness K and `G` the bs = 1 SellMatrix of the geometric stiffness' scalar factor on the same Graph
+        object (K_g = G (x) I3: compute_geometric_stiffness assembled like a scalar mass). `w` [n]: the Jacobi weights
+        with zeros on the fixed dofs. K is positive definite on the free dofs, K_g is indefinite, so the pencil is
+        turned round: G phi = theta K phi, lambda = -1 / theta, and the pairs of largest |theta| are found by block
+        subspace iteration with K-solves (eig_lowest refuses shifts and indefinite pencils). The start
+        block is eig_lowest's (host generator, `seed`, masked by w != 0, width m = modal_block(k, block)), followed by a
+        Rayleigh-Ritz on it. Per outer iteration: the right-hand sides -G X with the fixed rows zeroed; pcg_multi on K
+        from the warm start X diag(-theta) (exact for a converged column), every column to
+        sqrt(r.z) <= linear_tol sqrt(b.w b); one fem_spmm_km sweep for (K X, G X); fem_modal_gram; one device-to-host
+        read; rayleigh_ritz(X^T G X, X^T K X) on the host with its pairs reordered by |theta| descending;
+        fem_modal_rotate; fem_modal_residual with G X in the place of K X and K X in the place of M X. Column j has
+        converged when ||G x_j - theta_j K x_j|| <= tol |theta_j| ||K x_j|| over the free dofs; the solve stops when
+        the first k have. Same input, same bits.
+        PCG_BREAKDOWN: a Ritz value that is not finite, a Rayleigh-Ritz that fails, or every |theta| at or below
+        MODAL_THETA_FLOOR of the start block's largest (G = 0: no prestress). PCG_MAXITER: the outer cap, or an inner
+        solve that did not converge (inner_failed). No column locking. `timers` (a dict, for tools/bench_buckling.py):
+        the seconds of the inner solves, the sweeps and the rest are added to its "solve", "sweep" and "host" entries,
+        with a device synchronisation around each. Returns a BucklingResult."""
+        form, G = self._mass_form("buckling_lowest", G)
+        if form != C.MASS_SELL:
+            raise ValueError("buckling_lowest: G must be a bs = 1 SellMatrix (the scalar factor of K_g)")
+        if self.bs != 3:
+            raise ValueError(f"buckling_lowest: the stiffness must be a bs = 3 matrix, got bs = {self.bs}")
+        m = modal_block(k, block)
+        k = int(k)
+        if w is None or w.numel() != self.n:
+            raise ValueError(f"buckling_lowest: w must hold {self.n} values (Jacobi weights, zero on the fixed dofs)")
+        if max_iter < 0 or linear_max_iter < 1:
+            raise ValueError(f"buckling_lowest: max_iter >= 0 and linear_max_iter >= 1 needed, got {max_iter} and "
+                             f"{linear_max_iter}")
+        lib = C.lib()
+        dev, n = self.device, self.n
+        w = w.to(device=dev, dtype=F64).contiguous().view(-1)
+        free = (w != 0).to(F64)[:, None]
+        start = torch.randn((n, m), dtype=F64, generator=torch.Generator().manual_seed(int(seed)))
+        X, W, GX, KX = (torch.zeros((n, m), dtype=F64, device=dev) for _ in range(4))
+        X.copy_(start)
+        X.mul_(free)
+        # the modal kernels' nine slots X W P KX KW KP MX MW MP: G X takes KX's, K X takes MX's; P and the W products
+        # are never touched with one block (a = 1)
+        ptrs = (ctypes.c_void_p * 9)(*[v.data_ptr() for v in (X, W, W, GX, W, W, KX, W, W)])
+        work = torch.empty(int(lib.fem_modal_work_len()), dtype=F64, device=dev)
+        out = torch.zeros(C.MODAL_OUT_LEN, dtype=F64, device=dev)
+        coef = torch.zeros(3 * 64 + 8, dtype=F64, device=dev)     # C [m, m], then theta at 192
+        coef_host = torch.zeros(3 * 64 + 8, dtype=F64)
+        cols, dcols = self._multi_cols()
+        vals, gv = self.plain_values(), G.plain_values()
+        st = C.stream(dev)
+
+        def timed(name, fn, *args):
+            """fn(*args), its seconds added to timers[name] (with device synchronisations) when timers are kept."""
+            if timers is None:
+                return fn(*args)
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            r = fn(*args)
+            torch.cuda.synchronize(dev)
+            own[name] = own.get(name, 0.0) + time.perf_counter() - t0
+            return r
+
+        own = {}
+
+        def sweep():
+            C.check(lib.fem_spmm_km(self.g.n_nodes, self.bs, m, C.ptr(self.g.slice_ptr), cols, dcols, C.ptr(vals),
+                                    C.ptr(gv), form, C.ptr(X), C.ptr(KX), C.ptr(GX), st), "fem_spmm_km")
+
+        def ritz():
+            """Gram matrices of X, one read, Rayleigh-Ritz, |theta| descending -> (theta, C) or None."""
+            C.check(lib.fem_modal_gram(n, m, 1, ptrs, C.ptr(work), C.ptr(out), st), "fem_modal_gram")
+            host = out.cpu()
+            GG = host[: m * m].view(m, m)
+            GK = host[C.MODAL_OUT_GM: C.MODAL_OUT_GM + m * m].view(m, m)
+            rr = rayleigh_ritz(GG, GK, m)
+            if rr is None or not bool(torch.isfinite(rr[0]).all()):
+                return None
+            order = torch.argsort(rr[0].abs(), descending=True, stable=True)
+            return rr[0][order].clone(), rr[1][:, order].contiguous()
+
+        def rotate(theta, Cm):
+            coef_host.zero_()
+            coef_host[: m * m] = Cm.reshape(-1)
+            coef_host[192: 192 + m] = theta
+            coef.copy_(coef_host)
+            C.check(lib.fem_modal_rotate(n, m, 1, ptrs, C.ptr(coef), st), "fem_modal_rotate")
+
+        def result(theta, status, it, lin, rel, hist, inner=False):
+            th = theta[:k].clone()
+            h = torch.stack(hist) if hist else torch.zeros((0, k), dtype=F64)
+            return BucklingResult(-1.0 / th, th, X[:, :k].clone(), it, lin, status, rel, h if history else None, inner)
+
+        nan = torch.full((k,), float("nan"), dtype=F64)
+        t_all = time.perf_counter()
+        sweep()
+        rr = ritz()
+        if rr is None or not float(rr[0].abs().max()) > 0.0:
+            return result(torch.zeros(m, dtype=F64), C.PCG_BREAKDOWN, 0, 0, nan, [])
+        theta, Cm = rr
+        theta_ref = float(theta.abs().max())
+        rotate(theta, Cm)
+        hist, status, it, lin, rel = [], C.PCG_MAXITER, 0, 0, nan
+        for it in range(int(max_iter) + 1):
+            C.check(lib.fem_modal_residual(n, m, C.ptr(GX), C.ptr(KX), C.ptr(w), C.ptr(coef[192:]), C.ptr(W),
+                                           C.ptr(work), C.ptr(out), st), "fem_modal_residual")
+            host = out.cpu()
+            rn = host[C.MODAL_OUT_NORMS: C.MODAL_OUT_NORMS + m]
+            kn = host[C.MODAL_OUT_NORMS + m: C.MODAL_OUT_NORMS + 2 * m]
+            rel = (rn / (theta.abs() * kn))[:k].clone()
+            hist.append(rel)
+            if not bool(torch.isfinite(rel).all()):
+                status = C.PCG_BREAKDOWN
+                break
+            if bool((rel <= tol).all()):
+                status = C.PCG_CONVERGED
+                break
+            if it == max_iter:
+                break
+            B = GX.mul(free).neg_()
+            scale = torch.sqrt((w[:, None] * B * B).sum(dim=0)).cpu()
+            tols = [max(float(linear_tol) * float(s), 1e-300) for s in scale]
+            sol = timed("solve", lambda: self.pcg_multi(B, x0=X * (-theta).to(dev)[None, :], w=w, mode=C.MODE_PCG,
+                                                        tol=tols, max_iter=int(linear_max_iter)))
+            lin += max(sol.iterations)
+            if any(s != C.PCG_CONVERGED for s in sol.status):
+                return result(theta, C.PCG_MAXITER, it, lin, rel, hist, inner=True)
+            X.copy_(sol.x)
+            timed("sweep", sweep)
+            rr = ritz()
+            if rr is None or float(rr[0].abs().max()) <= MODAL_THETA_FLOOR * theta_ref:
+                status = C.PCG_BREAKDOWN
+                break
+            theta, Cm = rr
+            rotate(theta, Cm)
+        if timers is not None:   # everything that is neither an inner solve nor a sweep: Gram, Ritz, rotation, residual
+            torch.cuda.synchronize(dev)
+            own["host"] = time.perf_counter() - t_all - own.get("solve", 0.0) - own.get("sweep", 0.0)
+            for name, secs in own.items():
+                timers[name] = timers.get(name, 0.0) + secs
+        return result(theta, status, it, lin, rel, hist)
 
     # ---------------------------------------------------------------- combinations with the mass (csrc/transient.hip)
     def _held_values(self):

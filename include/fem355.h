@@ -1025,6 +1025,22 @@ int fem_iso_stress_thermal(const double* coords, const int64_t* conn, int64_t M,
                            const double* dN, const double* w, int n_ip, int layout, double* sig, double* vm,
                            fem_stream_t stream);
 
+/* ------------------------------------------------------------------ linear buckling (csrc/buckling.hip)
+ * fem_geo_scalar: the geometric (initial-stress) stiffness of c3d4 / c3d6 / c3d8 / c3d10 (npe = 4 / 6 / 8 / 10) as its
+ * scalar factor (the reference has no buckling analysis):
+ *   Gs[M, npe, npe], Gs_e[a][b] = sum_q w_q |detJ_q| grad N_a(q)^T sigma_q grad N_b(q),  K_g,e = Gs_e (x) I3
+ * -- the form of fem_iso_mass_scalar, so assembled as a bs = 1 matrix on the node pattern it takes every `mass` slot
+ * (fem_spmm_km, fem_sell_axpby_mass, fem_quadform_km). dN [n_ip, npe, 3] and w [n_ip] as fem_iso_mass_scalar
+ * (n_ip <= 32; c3d4: one point, the P1 derivatives, weight 1/6); |detJ_q| with its sign convention. The stress is
+ * formed inside the kernel at the points that integrate Gs: sigma_q = D(E, nu) B_q u_e when u [N, 3] is not NULL, plus
+ * the per-element constant sigma0 [M, 3, 3] (upper triangle read: what fem_iso_stress layout 0 / fem_tet4_stress
+ * write) when that is not NULL; both NULL is FEM_EARG. bad [M] bytes, zeroed by the caller: bad[e] is set to 1 for an
+ * element with detJ = 0 or not finite at a point (its block is then meaningless). Gs_e is symmetric bit for bit (the
+ * upper triangle is computed and mirrored). No atomics; FEM_EBADTYPE for another npe. */
+int fem_geo_scalar(const double* coords, const int64_t* conn, int64_t M, int npe, const double* u, double E, double nu,
+                   const double* sigma0, const double* dN, const double* w, int n_ip, double* Gs, uint8_t* bad,
+                   fem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
