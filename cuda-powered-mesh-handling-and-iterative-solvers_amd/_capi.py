@@ -217,6 +217,7 @@ SIGNATURES = {
     "fem_quadform_km": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "fem_tet4_nl": (_I, [_P, _P, _L, _P, _D, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fem_tet4_nl_gather": (_I, [_P, _P, _P, _L, _P, _D, _P, _P, _P, _P]),
+    "fem_tet4_j2": (_I, [_P, _P, _L, _P, _D, _D, _D, _D, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fem_shell_ke": (_I, [_P, _P, _L, _I, _P, _P, _I, _P, _P, _P, _P]),
     "fem_shell_geom": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fem_shell_apply": (_I, [_P, _P, _P, _I, _P, _P, _L, _P, _P, _P]),

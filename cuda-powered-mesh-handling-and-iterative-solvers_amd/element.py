@@ -916,6 +916,60 @@ def compute_c3d4_deformation_gradient(coords, elements, displacement, device="cu
     return _out(Fm, device, dtype), _out(det, device, dtype)
 
 
+# ============================================================================ elastoplastic c3d4 (csrc/plasticity.hip)
+# Small-strain von Mises (J2) plasticity with linear isotropic hardening, integrated by the radial return
+# (include/fem355.h fem_tet4_j2). No counterpart in the reference, whose materials are all elastic.
+PlasticState = _sys.PlasticState
+
+
+class PlasticUpdate:
+    """Result of compute_c3d4_plastic_update: K [M,12,12] (None without the tangent), forces [M,4,3], energy [M] (the
+    incremental potential), stress [M,6], state (the trial PlasticState) and plastic [M] bool (True where the element
+    yielded in this update)."""
+    __slots__ = ("K", "forces", "energy", "stress", "state", "plastic")
+
+    def __init__(self, K, forces, energy, stress, state, plastic):
+        self.K, self.forces, self.energy, self.stress, self.state, self.plastic = K, forces, energy, stress, state, \
+            plastic
+
+
+def compute_c3d4_plastic_update(coords, elements, displacement, E, nu, yield_stress, hardening, state=None,
+                                tangent=True, device="cuda:0", dtype=torch.float32):
+    """One return-mapping update of every c3d4 element at `displacement` [N,3] from the committed `state` (a
+    PlasticState; None: virgin): small-strain J2 plasticity with the yield stress `yield_stress` + `hardening` x
+    accumulated plastic strain. Returns a PlasticUpdate: the consistent tangent K [M,12,12] (exactly symmetric; None
+    with tangent=False, which gives the same bits everywhere else), the element forces [M,4,3], the incremental
+    potential [M] whose derivative in the element's displacements is the force, the stress [M,6] and the plastic strain
+    [M,6] as tensor components (xx, yy, zz, xy, yz, xz), the trial state and which elements yielded. `state` is not
+    modified. ValueError for a degenerate element and for E <= 0, nu outside (-1, 0.5), yield_stress <= 0,
+    hardening < 0 or a state of the wrong shape."""
+    what = "compute_c3d4_plastic_update"
+    _sys.check_plastic_material(what, E, nu, yield_stress, hardening)
+    if elements.dim() != 2 or elements.shape[1] != 4:
+        raise ValueError(f"c3d4 expects 4 nodes per element, got {list(elements.shape)}")
+    M = elements.shape[0]
+    _sys.check_plastic_state(what, state, M)
+    lib = C.lib()
+    dev, coords, elements = _prep(coords, elements, device)
+    u = _disp(displacement, dev, coords.shape[0])
+    e = lambda *s: torch.empty(s, dtype=F64, device=dev)
+    K = e(M, 12, 12) if tangent else None
+    fe, we, sig, ep, al = e(M, 4, 3), e(M), e(M, 6), e(M, 6), e(M)
+    pl = torch.empty(M, dtype=torch.uint8, device=dev)
+    ep_in = al_in = None
+    if state is not None:
+        ep_in = state.plastic_strain.to(device=dev, dtype=F64).contiguous()
+        al_in = state.equivalent_plastic_strain.to(device=dev, dtype=F64).contiguous()
+    bad = _bad_scalar(dev, M)
+    C.check(lib.fem_tet4_j2(C.ptr(coords), C.ptr(elements), M, C.ptr(u), float(E), float(nu), float(yield_stress),
+                            float(hardening), C.ptr(ep_in), C.ptr(al_in), 0, C.ptr(K), C.ptr(fe), C.ptr(we),
+                            C.ptr(sig), C.ptr(ep), C.ptr(al), C.ptr(pl), C.ptr(bad), C.stream(dev)), "fem_tet4_j2")
+    _raise_if_singular(bad, M)
+    o = lambda t: _out(t, device, dtype)
+    return PlasticUpdate(None if K is None else o(K), o(fe), o(we), o(sig), PlasticState(o(ep), o(al)),
+                         pl.to(torch.device(device)) != 0)
+
+
 # ============================================================================ geometric stiffness (csrc/buckling.hip)
 # K_g(sigma) of a linear prestress for c3d4 / c3d6 / c3d8 / c3d10: the matrix of linear buckling (K + lambda K_g) phi = 0
 # and of stress-stiffened modes (DESIGN §8r). The reference has neither.
@@ -1001,6 +1055,8 @@ __all__ += [
     "compute_c3d4_tangent_K_matrix", "compute_c3d4_internal_forces", "compute_c3d4_strain_energy",
     "compute_c3d4_cauchy_stress", "compute_c3d4_deformation_gradient",
 ]
+
+__all__ += ["compute_c3d4_plastic_update", "PlasticState"]
 
 __all__ += [
     "compute_stress_tensor", "compute_von_mises_stress", "compute_element_stress", "compute_c3d4_element_stress",

@@ -961,6 +961,9 @@ def transient_solver(K, M, elements, F, fixed, num_nodes, dt, steps, amplitude=N
 # The reference's own newton_raphson_solver (`solver/solver.py:978-1065`, secant form on a caller's K(u)) follows.
 _LS_HALVINGS = 10
 _LS_C1 = 1e-4
+# elastoplastic solves: a trial taken for its smaller residual may raise the potential by no more than this share of
+# (|internal energy| + |load work|), the rounding of the potential's two sums
+_LS_POT_ROUND = 1e-13
 
 
 def _check_nonlinear(what, coords, elements, F, fixed, material, load_steps, tol, atol, max_iter, linear_rtol,
@@ -988,15 +991,26 @@ def _check_nonlinear(what, coords, elements, F, fixed, material, load_steps, tol
     return _fixed_ids(what, fixed, N)
 
 
-def _newton_statics_loop(ns, Fd, u, load_steps, tol, atol, max_iter, linear_rtol, linear_max_iter, on_iteration=None):
+def _newton_statics_loop(ns, Fd, u, load_steps, tol, atol, max_iter, linear_rtol, linear_max_iter, on_iteration=None,
+                         load_factors=None, after_step=None, potential_round=None, first_tangent=None):
     """The load-stepped Newton iteration of nonlinear_static_solver on a system.NewtonStatics -> NonlinearResult (u
-    left on the device). on_iteration(dict): per-iteration record hook of tools/bench_nonlinear.py."""
+    left on the device). on_iteration(dict): per-iteration record hook of tools/bench_nonlinear.py.
+    load_factors: the load factor of every step in order (default s / load_steps); the stop rule then scales with
+    max |load factor|, so that a step to a zero load keeps a tolerance. after_step(s, u): called after every converged
+    step (the elastoplastic solver commits its state there). potential_round: a trial accepted for its smaller residual
+    must also keep the potential within potential_round (|internal energy| + |load work|) of the iterate's; a
+    potential that is convex but only piecewise smooth can otherwise cycle under full Newton steps. first_tangent():
+    fills the matrix in the first iteration of every step in place of ns.tangent()."""
     free = ns.mask == 0
     stop = max(float(tol) * float(torch.linalg.vector_norm(Fd[free])), float(atol))
+    if load_factors is not None:
+        load_factors = [float(f) for f in load_factors]
+        stop = max(float(tol) * max(abs(f) for f in load_factors) * float(torch.linalg.vector_norm(Fd[free])),
+                   float(atol))
     res = _sys.NonlinearResult(u, False, _sys.NL_OK, "", [], [], [], [])
-    S = int(load_steps)
+    S = int(load_steps) if load_factors is None else len(load_factors)
     for s in range(1, S + 1):
-        lf = s / S
+        lf = s / S if load_factors is None else load_factors[s - 1]
         print(f"Load step {s}/{S}")
         norms, pits, alphas = [], [], []
         res.newton_iterations.append(0)
@@ -1005,7 +1019,8 @@ def _newton_statics_loop(ns, Fd, u, load_steps, tol, atol, max_iter, linear_rtol
         res.step_lengths.append(alphas)
         done = False
         for k in range(1, int(max_iter) + 1):
-            r, en, rn, inv = ns.evaluate(u, lf, Fd, tangent=True)
+            own = first_tangent is not None and k == 1
+            r, en, rn, inv = ns.evaluate(u, lf, Fd, tangent=not own)
             if inv is not None:   # only a caller's u_init can be inverted here: trial points are rejected below
                 en = float("inf")
             print(f"Iteration {k}, Residual Norm: {rn}")
@@ -1015,7 +1030,10 @@ def _newton_statics_loop(ns, Fd, u, load_steps, tol, atol, max_iter, linear_rtol
                 done = True
                 break
             pot = en - lf * ns.work
-            ns.tangent()
+            if own:
+                first_tangent()
+            else:
+                ns.tangent()
             w = ns.jacobi()
             delta, it, stt = ns.solve_increment(r, w, linear_rtol, linear_max_iter)
             slope = float(torch.dot(r, delta))
@@ -1035,7 +1053,10 @@ def _newton_statics_loop(ns, Fd, u, load_steps, tol, atol, max_iter, linear_rtol
                 ut = u + alpha * delta
                 _, en_t, rn_t, inv_t = ns.evaluate(ut, lf, Fd, tangent=False)
                 evals += 1
-                if inv_t is None and (en_t - lf * ns.work <= pot - _LS_C1 * alpha * slope or rn_t < rn):
+                pot_t = en_t - lf * ns.work
+                lower = rn_t < rn and (potential_round is None or
+                                       pot_t <= pot + potential_round * (abs(en_t) + abs(lf * ns.work)))
+                if inv_t is None and (pot_t <= pot - _LS_C1 * alpha * slope or lower):
                     accepted = True
                     break
                 alpha *= 0.5
@@ -1058,6 +1079,8 @@ def _newton_statics_loop(ns, Fd, u, load_steps, tol, atol, max_iter, linear_rtol
             res.message = f"Load step {s} did not converge within {int(max_iter)} iterations."
             res.u = u
             return res
+        if after_step is not None:
+            after_step(s, u)
     res.u = u
     res.converged = True
     return res
@@ -1099,6 +1122,95 @@ def nonlinear_static_solver(coords, elements, F, fixed, E, nu, material="svk", l
     ns = _sys.NewtonStatics(coords, el, E, nu, material, mask.view(-1), graph=cached_graph(el, N))
     try:
         res = _newton_statics_loop(ns, Fd, u, load_steps, tol, atol, max_iter, linear_rtol, linear_max_iter)
+    finally:
+        ns.close()
+    res.u = res.u.view(N, 3).to(device=torch.device(device), dtype=dtype)
+    return (res.u, res) if return_info else res.u
+
+
+# ============================================================================ elastoplastic statics
+# Small-strain von Mises plasticity with linear isotropic hardening on c3d4 meshes: the same Newton loop on
+# system.PlasticStatics (the return-mapping kernel of csrc/plasticity.hip; DESIGN §8s). No counterpart in the reference.
+def _fixed_mask(what, fixed, N):
+    """[N,3] bool of the dofs held at zero, from node ids or from a bool / uint8 [N,3] mask (per-dof supports)."""
+    if torch.is_tensor(fixed) and fixed.dim() == 2 and fixed.dtype in (torch.bool, torch.uint8):
+        if tuple(fixed.shape) != (N, 3):
+            raise ValueError(f"{what}: a fixed-dof mask must be [{N}, 3], got {tuple(fixed.shape)}")
+        return fixed.to("cpu") != 0
+    mask = torch.zeros((N, 3), dtype=torch.bool)
+    mask[_fixed_ids(what, fixed, N)] = True
+    return mask
+
+
+def elastoplastic_static_solver(coords, elements, F, fixed, E, nu, yield_stress, hardening, load_path=None,
+                                load_steps=1, state=None, tol=1e-8, atol=0.0, max_iter=25, linear_rtol=1e-6,
+                                linear_max_iter=10000, u_init=None, device="cuda:0", dtype=torch.float64,
+                                return_info=False):
+    """Elastoplastic statics of a c3d4 mesh: small-strain, rate-independent von Mises (J2) plasticity with linear
+    isotropic hardening (yield stress `yield_stress` + `hardening` x accumulated plastic strain), associative flow,
+    integrated by the radial return with its consistent tangent (csrc/plasticity.hip).
+    load_path: load factors applied in order, e.g. [0.5, 1.0, 0.0] for load and unload (default k / load_steps,
+    k = 1..load_steps). Each factor runs the Newton iteration of nonlinear_static_solver from the previous u on the
+    incremental potential of the step, then commits the material state; `state` (a PlasticState) is the state before
+    the first step (default virgin). fixed: node ids, or a bool / uint8 [N,3] mask of single dofs held at zero
+    (rollers). The stop rule is nonlinear_static_solver's with the scale max |load factor| ||F_free||_2. In the line
+    search a trial taken for its smaller residual must not raise the potential beyond its rounding. The first
+    iteration of every step takes the elastic tangent: at the displacement just committed every yielded element has
+    f_tr = 0 up to rounding, so the branch of its consistent tangent is noise there, and a plastic tangent on elements
+    that unload overshoots; from the second iteration on the consistent tangent is used.
+    Never raises on non-convergence: NonlinearResult.status is MAX_ITER / LINE_SEARCH_FAILED / LINEAR_SOLVE_FAILED,
+    failed_step names the step, u is the last accepted iterate and state the committed state of the last converged
+    step. hardening = 0 (perfect plasticity) is accepted but may stall at the limit load: the tangent is then only
+    semi-definite there and the PCG has no positive definite matrix.
+    Limits: c3d4 only, small strains, isotropic linear hardening, associative J2 flow, homogeneous Dirichlet data, one
+    GPU, the assembled operator, one material for the whole mesh. Out of scope: other element types, finite-strain
+    plasticity, kinematic or nonlinear hardening, arc-length control, a matrix-free tangent, multi-GPU, per-element
+    yield data.
+    Returns u in `dtype` on `device`; with return_info also the system.NonlinearResult with state (the final
+    PlasticState), stress [M,6] at u (xx, yy, zz, xy, yz, xz) and plastic_fraction per converged step."""
+    what = "elastoplastic_static_solver"
+    if load_path is not None:
+        load_path = [float(f) for f in load_path]
+        if not load_path or not all(f == f and abs(f) != float("inf") for f in load_path):
+            raise ValueError(f"{what}: load_path must hold at least one finite load factor")
+    _check_nonlinear(what, coords, elements, F, [], "svk", load_steps, tol, atol, max_iter, linear_rtol,
+                     linear_max_iter, u_init)
+    N, M = coords.shape[0], elements.shape[0]
+    mask = _fixed_mask(what, fixed, N)
+    _sys.check_plastic_material(what, E, nu, yield_stress, hardening)
+    _sys.check_plastic_state(what, state, M)
+    if load_path is None:
+        load_path = [k / int(load_steps) for k in range(1, int(load_steps) + 1)]
+    dev = _dev(device)
+    coords = coords.to(device=dev, dtype=F64).contiguous()
+    el = elements.to(device=dev, dtype=LONG).contiguous()
+    mask = mask.to(device=dev, dtype=torch.uint8).contiguous()
+    Fd = F.to(device=dev, dtype=F64).reshape(-1).contiguous()
+    u = torch.zeros(3 * N, dtype=F64, device=dev) if u_init is None else \
+        u_init.to(device=dev, dtype=F64).reshape(-1).clone()
+    u[mask.view(-1) != 0] = 0.0
+    if state is not None:
+        state = _sys.PlasticState(state.plastic_strain.to(device=dev, dtype=F64),
+                                  state.equivalent_plastic_strain.to(device=dev, dtype=F64))
+    ns = _sys.PlasticStatics(coords, el, E, nu, yield_stress, hardening, mask.view(-1), graph=cached_graph(el, N),
+                             state=state)
+    fractions = []
+
+    def after_step(s, u_s):
+        fractions.append(ns.plastic_fraction())
+        ns.commit()
+
+    try:
+        res = _newton_statics_loop(ns, Fd, u, len(load_path), tol, atol, max_iter, linear_rtol, linear_max_iter,
+                                   load_factors=load_path, after_step=after_step, potential_round=_LS_POT_ROUND,
+                                   first_tangent=ns.elastic_tangent)
+        out = torch.device(device)
+        res.state = _sys.PlasticState(*(x.to(out) for x in (ns.state().plastic_strain,
+                                                           ns.state().equivalent_plastic_strain)))
+        res.stress = ns.stress(res.u).to(out) if M else torch.zeros((0, 6), dtype=F64, device=out)
+        res.plastic_fraction = fractions
+        if not res.converged:
+            res.failed_step = len(res.newton_iterations)
     finally:
         ns.close()
     res.u = res.u.view(N, 3).to(device=torch.device(device), dtype=dtype)

@@ -2116,6 +2116,11 @@ class NonlinearResult:
     residual_norms: list = None
     pcg_iterations: list = None
     step_lengths: list = None
+    # solver.elastoplastic_static_solver only (None elsewhere)
+    state: "PlasticState" = None     # committed state after the last converged step
+    stress: torch.Tensor = None      # [M,6] at the returned u (xx, yy, zz, xy, yz, xz)
+    plastic_fraction: list = None    # per converged step: the share of elements that yielded in it
+    failed_step: int = None          # 1-based index in the load path of the step that did not converge
 
 
 @_scoped
@@ -2129,13 +2134,18 @@ class NewtonStatics:
     def __init__(self, coords, elements, E, nu, material, fixed_mask, graph: Graph = None):
         if material not in C.MATERIALS:
             raise ValueError(f"Unknown material {material!r} (supported: {', '.join(sorted(C.MATERIALS))}).")
+        self._setup(coords, elements, E, nu, fixed_mask, graph)
+        self.mat = C.MATERIALS[material]
+
+    def _setup(self, coords, elements, E, nu, fixed_mask, graph):
+        """Everything but the material: the graph, the matrix and the buffers (shared with PlasticStatics)."""
         self.lib = C.lib()
         self.device = dev = coords.device
         self.coords = coords.to(F64).contiguous()
         self.elements = elements.to(I64).contiguous()
         if self.elements.dim() != 2 or self.elements.shape[1] != 4:
             raise ValueError(f"NewtonStatics: c3d4 connectivity [M, 4] expected, got {tuple(self.elements.shape)}")
-        self.E, self.nu, self.mat = float(E), float(nu), C.MATERIALS[material]
+        self.E, self.nu = float(E), float(nu)
         self.N, self.M = self.coords.shape[0], self.elements.shape[0]
         self.g = graph if graph is not None else build_graph(self.elements, self.N)
         self.A = SellMatrix(self.g, 3)
@@ -2160,18 +2170,23 @@ class NewtonStatics:
             raise ValueError(f"NewtonStatics: {what} must hold {3 * self.N} values, got {x.numel()}")
         return x
 
+    def _element(self, u, tangent, forces):
+        """One element-kernel launch at u: the packed tangent into Kp (tangent) and / or fe, we (forces)."""
+        self.idx.fill_(self.M)
+        C.check(self.lib.fem_tet4_nl(C.ptr(self.coords), C.ptr(self.elements), self.M, C.ptr(u), self.E, self.nu,
+                                     self.mat, 1, C.ptr(self.Kp) if tangent else None,
+                                     C.ptr(self.fe) if forces else None, C.ptr(self.we) if forces else None,
+                                     None, None, C.ptr(self.idx[0:1]), C.ptr(self.idx[1:2]), self._stream),
+                "fem_tet4_nl")
+        self.launches += 1
+
     def evaluate(self, u, load_factor, fext, tangent=False):
         """r = load_factor fext - f_int(u) (0 on the fixed dofs) -> (r, internal energy, ||r||_2, inverted): one
         fem_tet4_nl launch (tangent: also the packed tangent, kept for `tangent()`), one gather, and ONE small
         device-to-host copy for the scalars. r is this object's buffer, overwritten by the next call. inverted: the
         lowest element with det F <= 0, or None (the energy is then +inf). The energies are summed in a fixed order."""
         u, fext = self._vec(u, "u"), self._vec(fext, "fext")
-        self.idx.fill_(self.M)
-        C.check(self.lib.fem_tet4_nl(C.ptr(self.coords), C.ptr(self.elements), self.M, C.ptr(u), self.E, self.nu,
-                                     self.mat, 1, C.ptr(self.Kp) if tangent else None, C.ptr(self.fe), C.ptr(self.we),
-                                     None, None, C.ptr(self.idx[0:1]), C.ptr(self.idx[1:2]), self._stream),
-                "fem_tet4_nl")
-        self.launches += 1
+        self._element(u, tangent, True)
         self._kp_ok = bool(tangent)
         C.check(self.lib.fem_tet4_nl_gather(C.ptr(self.fe), C.ptr(self.g.inc_ptr), C.ptr(self.g.inc), self.N,
                                             C.ptr(fext), float(load_factor), C.ptr(self.mask), None, C.ptr(self.r),
@@ -2190,12 +2205,11 @@ class NewtonStatics:
         if u is not None or not self._kp_ok:
             if u is None:
                 raise ValueError("NewtonStatics.tangent: no tangent evaluated yet; pass u")
-            u = self._vec(u, "u")
-            self.idx.fill_(self.M)
-            C.check(self.lib.fem_tet4_nl(C.ptr(self.coords), C.ptr(self.elements), self.M, C.ptr(u), self.E, self.nu,
-                                         self.mat, 1, C.ptr(self.Kp), None, None, None, None, C.ptr(self.idx[0:1]),
-                                         C.ptr(self.idx[1:2]), self._stream), "fem_tet4_nl")
-            self.launches += 1
+            self._element(self._vec(u, "u"), True, False)
+        return self._refill()
+
+    def _refill(self):
+        """The matrix from the packed tangent in Kp: reset() + add_element_matrices_sym."""
         self._kp_ok = False
         self.A.reset()
         if self.M:
@@ -2250,6 +2264,119 @@ class NewtonStatics:
             self.close()
         except Exception:
             pass
+
+
+@dataclass
+class PlasticState:
+    """Material state of an elastoplastic c3d4 mesh, one integration point per element: the plastic strain [M,6]
+    (deviatoric; tensor components in the order xx, yy, zz, xy, yz, xz) and the accumulated (equivalent) plastic
+    strain [M] >= 0."""
+    plastic_strain: torch.Tensor
+    equivalent_plastic_strain: torch.Tensor
+
+    @classmethod
+    def virgin(cls, M, device="cuda:0"):
+        return cls(torch.zeros((int(M), 6), dtype=F64, device=device), torch.zeros(int(M), dtype=F64, device=device))
+
+
+def check_plastic_material(what, E, nu, yield_stress, hardening):
+    """The ValueErrors of the elastoplastic entry points (fem_tet4_j2's FEM_EARG conditions), before any device call."""
+    if not float(E) > 0.0:
+        raise ValueError(f"{what}: E must be > 0, got {E}")
+    if not -1.0 < float(nu) < 0.5:
+        raise ValueError(f"{what}: nu must lie in (-1, 0.5), got {nu}")
+    if not float(yield_stress) > 0.0:
+        raise ValueError(f"{what}: yield_stress must be > 0, got {yield_stress}")
+    if not float(hardening) >= 0.0:
+        raise ValueError(f"{what}: hardening must be >= 0, got {hardening}")
+
+
+def check_plastic_state(what, state, M):
+    if state is None:
+        return
+    ep, al = getattr(state, "plastic_strain", None), getattr(state, "equivalent_plastic_strain", None)
+    if not torch.is_tensor(ep) or not torch.is_tensor(al) or tuple(ep.shape) != (M, 6) or tuple(al.shape) != (M,):
+        raise ValueError(f"{what}: state must be a PlasticState with plastic_strain [{M}, 6] and "
+                         f"equivalent_plastic_strain [{M}]")
+
+
+_UNREACHABLE_YIELD = 1e300
+
+
+@_scoped
+class PlasticStatics(NewtonStatics):
+    """Device state of an elastoplastic c3d4 statics solve: NewtonStatics with the J2 return-mapping kernel
+    of csrc/plasticity.hip in place of the hyperelastic one, plus two sets of state buffers allocated once. evaluate()
+    reads the committed set and writes the trial set, so the trial points of a line search leave no trace; commit()
+    swaps the two after a converged load step. The energy evaluate() returns is the incremental potential of the step."""
+
+    def __init__(self, coords, elements, E, nu, yield_stress, hardening, fixed_mask, graph: Graph = None, state=None):
+        check_plastic_material("PlasticStatics", E, nu, yield_stress, hardening)
+        self._setup(coords, elements, E, nu, fixed_mask, graph)
+        check_plastic_state("PlasticStatics", state, self.M)
+        self.sigma_y, self.hardening = float(yield_stress), float(hardening)
+        m = max(self.M, 1)
+        z = lambda *s: torch.zeros(s, dtype=F64, device=self.device)
+        self._st = [(z(m, 6), z(m)), (z(m, 6), z(m))]
+        self._c = 0               # index of the committed set; the other one takes the trial states
+        self._trial_ok = False    # the trial set holds the state of the last evaluate
+        self.plastic = torch.zeros(m, dtype=torch.uint8, device=self.device)   # 1 where the last evaluate yielded
+        if state is not None and self.M:
+            self._st[0][0][: self.M].copy_(state.plastic_strain)
+            self._st[0][1][: self.M].copy_(state.equivalent_plastic_strain)
+
+    def _j2(self, u, Kp, fe, we, sigma, trial, plastic, sigma_y=None):
+        ep, al = self._st[self._c]
+        ep_t, al_t = self._st[1 - self._c] if trial else (None, None)
+        self.idx.fill_(self.M)
+        C.check(self.lib.fem_tet4_j2(C.ptr(self.coords), C.ptr(self.elements), self.M, C.ptr(u), self.E, self.nu,
+                                     self.sigma_y if sigma_y is None else sigma_y, self.hardening, C.ptr(ep),
+                                     C.ptr(al), 1, C.ptr(Kp), C.ptr(fe),
+                                     C.ptr(we), C.ptr(sigma), C.ptr(ep_t), C.ptr(al_t), C.ptr(plastic),
+                                     C.ptr(self.idx[0:1]), self._stream), "fem_tet4_j2")
+        self.launches += 1
+
+    def _element(self, u, tangent, forces):
+        self._j2(u, self.Kp if tangent else None, self.fe if forces else None, self.we if forces else None, None,
+                 forces, self.plastic if forces else None)
+        self._trial_ok = self._trial_ok or bool(forces)
+
+    def elastic_tangent(self):
+        """Refill the matrix with the elastic tangent (the kernel's tangent under an unreachable yield stress; it does
+        not depend on u). The Newton loop takes it in the first iteration of a load step: at the u just committed every
+        yielded element has f_tr = 0 up to rounding, so which branch its consistent tangent takes there is noise, and a
+        plastic tangent on elements that unload overshoots. Returns the SellMatrix."""
+        self._j2(self.x.zero_(), self.Kp, None, None, None, False, None, sigma_y=_UNREACHABLE_YIELD)
+        return self._refill()
+
+    def commit(self):
+        """The trial state of the last evaluate() becomes the committed state (a swap of the two buffer sets)."""
+        if not self._trial_ok:
+            raise ValueError("PlasticStatics.commit: no evaluate() since the last commit")
+        self._c = 1 - self._c
+        self._trial_ok = False
+
+    def state(self):
+        """The committed state -> PlasticState (copies)."""
+        ep, al = self._st[self._c]
+        return PlasticState(ep[: self.M].clone(), al[: self.M].clone())
+
+    def trial_state(self):
+        """The state the last evaluate() would commit -> PlasticState (copies)."""
+        if not self._trial_ok:
+            raise ValueError("PlasticStatics.trial_state: no evaluate() since the last commit")
+        ep, al = self._st[1 - self._c]
+        return PlasticState(ep[: self.M].clone(), al[: self.M].clone())
+
+    def plastic_fraction(self):
+        """Share of the elements that yielded in the last evaluate()."""
+        return float(self.plastic[: self.M].to(F64).mean()) if self.M else 0.0
+
+    def stress(self, u):
+        """sigma [M,6] at u from the committed state; neither state set is written."""
+        out = torch.empty((max(self.M, 1), 6), dtype=F64, device=self.device)
+        self._j2(self._vec(u, "u"), None, None, None, out, False, None)
+        return out[: self.M]
 
 
 def assemble_tet4_system(coords, elements, kind="poisson", E=1.0, nu=0.0, graph=None):

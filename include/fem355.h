@@ -942,6 +942,35 @@ int fem_tet4_nl(const double* coords, const int64_t* conn, int64_t M, const doub
 int fem_tet4_nl_gather(const double* fe, const int32_t* inc_ptr, const int32_t* inc, int64_t N, const double* fext,
                        double load_factor, const uint8_t* mask, double* fint, double* r, fem_stream_t stream);
 
+/* ------------------------------------------------------------------ elastoplastic statics (csrc/plasticity.hip)
+ * Small-strain, rate-independent von Mises (J2) plasticity with linear isotropic hardening on c3d4 (no
+ * counterpart in the reference, whose materials are all elastic). With the gradients g_a and volume V of fem_tet4_geom,
+ * eps = sym(sum_a u_a (x) g_a), mu = E / (2 (1 + nu)), kappa = E / (3 (1 - 2 nu)); every tensor in
+ * fem_voigt_to_tensor's order (xx, yy, zz, xy, yz, xz) as TENSOR components (no engineering factor 2). Committed state
+ * per element: the plastic strain ep_n [M,6] (deviatoric) and the accumulated plastic strain alpha_n [M] >= 0.
+ *   e = dev eps, s_tr = 2 mu (e - ep_n), q_tr = sqrt(3/2) |s_tr|, f_tr = q_tr - (sigma_y + H alpha_n)
+ *   f_tr <= 0: s = s_tr, state unchanged, C = kappa 1(x)1 + 2 mu P_dev
+ *   f_tr >  0: dgamma = f_tr / (3 mu + H), n = s_tr / |s_tr|, beta = 1 - 3 mu dgamma / q_tr, s = beta s_tr,
+ *              ep_n+1 = ep_n + sqrt(3/2) dgamma n, alpha_n+1 = alpha_n + dgamma,
+ *              C = kappa 1(x)1 + 2 mu beta P_dev - 2 mu (3 mu / (3 mu + H) - (1 - beta)) n(x)n
+ * fem_tet4_j2: per element the consistent tangent Kt = V B^T C B (packed != 0: the upper 3x3 blocks in
+ *   fem_iso_ke_sym's layout for npe = 4, which fem_assemble_from_ke_sym consumes; else the full [M,12,12] whose upper
+ *   blocks are the packed ones bit for bit and whose lower blocks are their transposes), the forces fe [M,4,3] =
+ *   V sigma g_a with sigma = kappa tr(eps) 1 + s, the incremental potential we [M] = V (kappa/2 tr(eps)^2 +
+ *   mu |e - ep_n+1|^2 + H/2 alpha_n+1^2 + sigma_y dgamma) whose derivative in the element's 12 displacements is fe while
+ *   the committed state is fixed, sigma [M,6], the trial state ep_out [M,6] / alpha_out [M] and plastic [M] = 1 where
+ *   f_tr > 0. ep_in == alpha_in == NULL is the virgin state (zeros). Every output may be NULL; Kt == NULL runs a build
+ *   without the tangent work (the same bits in every other output). ep_out / alpha_out may alias ep_in / alpha_in: an
+ *   element reads and writes only its own slot. *bad_idx (nullable): as fem_tet4_ke (device int64 preset to M,
+ *   |det[1 x y z]| < 1e-12); such an element writes zeros to Kt, fe, we, sigma, plastic and copies its input state
+ *   through. M == 0: FEM_OK, no launch. FEM_EARG: sigma_y <= 0, H < 0, nu outside (-1, 0.5), only one of ep_in /
+ *   alpha_in. H = 0 (perfect plasticity) is accepted; the tangent is then only semi-definite at the limit load.
+ *   The residual is gathered from fe by fem_tet4_nl_gather. */
+int fem_tet4_j2(const double* coords, const int64_t* conn, int64_t M, const double* u, double E, double nu,
+                double sigma_y, double H, const double* ep_in, const double* alpha_in, int packed, double* Kt,
+                double* fe, double* we, double* sigma, double* ep_out, double* alpha_out, uint8_t* plastic,
+                int64_t* bad_idx, fem_stream_t stream);
+
 /* ------------------------------------------------------------------ shell elements (csrc/shell.hip)
  * Flat s3 / s4 shells with 6 dofs per node (u, v, w, thx, thy, thz) -- the reference's `solver/shell.py`, formulation
  * quirks included: frame unit = [a; b; c] from edge 0->1 and edge 0->2 (npe 3) / 0->3 (npe 4), local
