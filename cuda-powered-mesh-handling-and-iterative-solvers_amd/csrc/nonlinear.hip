@@ -51,8 +51,34 @@ __device__ __forceinline__ double nl_entry(const double* __restrict__ r, int a, 
     return s * r[NL_V];
 }
 
+// a b - c d with the rounding error of c d carried along (Kahan): within 1.5 ulp of the exact difference, where the
+// plain form loses every digit the two products share
+__device__ __forceinline__ double nl_dop(double a, double b, double c, double d) {
+#pragma clang fp contract(off)
+    const double w = c * d;
+    const double e = fma(-c, d, w);
+    const double f = fma(a, b, -w);
+    return f + e;
+}
+
+// x0 y0 + x1 y1 + x2 y2 with the errors of the products and of the two sums collected and added once
+__device__ __forceinline__ double nl_dot3c(double x0, double y0, double x1, double y1, double x2, double y2) {
+#pragma clang fp contract(off)
+    const double p0 = x0 * y0, p1 = x1 * y1, p2 = x2 * y2;
+    const double e0 = fma(x0, y0, -p0), e1 = fma(x1, y1, -p1), e2 = fma(x2, y2, -p2);
+    const double s = p0 + p1;
+    const double b1 = s - p0;
+    const double t1 = (p0 - (s - b1)) + (p1 - b1);
+    const double s2 = s + p2;
+    const double b2 = s2 - s;
+    const double t2 = (s - (s2 - b2)) + (p2 - b2);
+    return s2 + ((t1 + t2) + ((e0 + e1) + e2));
+}
+
 // One lane: everything of element e that does not depend on the output entry, into the record r and the per-element
-// outputs. An inverted element (det F <= 0) or a degenerate reference element gets a zero record, zero stress and
+// outputs. det F and the cofactors of F are formed by nl_dop / nl_dot3c: a deformation gradient with entries far above
+// its determinant (a sliver mesh carrying a finite strain: F ~ 1e3, J ~ 1) left the plain cofactor expansion 35 x
+// less accurate than the rounding of F itself allows (tests/test_gpu_hard_geometry_nl.py). An inverted element (det F <= 0) or a degenerate reference element gets a zero record, zero stress and
 // energy +inf; no logarithm of a non-positive number is taken and no NaN is stored. Products are not fused into sums
 // here either, so the TAN = false build gives the forces and energies of the TAN = true build bit for bit.
 template <int MAT, bool TAN>
@@ -87,10 +113,10 @@ __device__ __forceinline__ void nl_element(const double* __restrict__ X, const i
         for (int j = 0; j < 3; ++j) F[i][j] = (i == j ? 1.0 : 0.0) + H[i][j];
     // cofactors of F (Cf[i][j] = cofactor of F[i][j]); det F by the first row
     double Cf[3][3];
-    Cf[0][0] = F[1][1] * F[2][2] - F[1][2] * F[2][1];
-    Cf[0][1] = F[1][2] * F[2][0] - F[1][0] * F[2][2];
-    Cf[0][2] = F[1][0] * F[2][1] - F[1][1] * F[2][0];
-    const double J = (F[0][0] * Cf[0][0] + F[0][1] * Cf[0][1]) + F[0][2] * Cf[0][2];
+    Cf[0][0] = nl_dop(F[1][1], F[2][2], F[1][2], F[2][1]);
+    Cf[0][1] = nl_dop(F[1][2], F[2][0], F[1][0], F[2][2]);
+    Cf[0][2] = nl_dop(F[1][0], F[2][1], F[1][1], F[2][0]);
+    const double J = nl_dot3c(F[0][0], Cf[0][0], F[0][1], Cf[0][1], F[0][2], Cf[0][2]);
     const bool ok = !degenerate && J > 0.0;   // false for a NaN as well
     if (detF) detF[e] = (degenerate || J != J) ? 0.0 : J;
     if (!ok) {
@@ -175,12 +201,12 @@ __device__ __forceinline__ void nl_element(const double* __restrict__ X, const i
                 for (int i = 0; i < 3; ++i) r[NL_X + 3 * a + i] = Fg[a][i];
         }
     } else {
-        Cf[1][0] = F[0][2] * F[2][1] - F[0][1] * F[2][2];
-        Cf[1][1] = F[0][0] * F[2][2] - F[0][2] * F[2][0];
-        Cf[1][2] = F[0][1] * F[2][0] - F[0][0] * F[2][1];
-        Cf[2][0] = F[0][1] * F[1][2] - F[0][2] * F[1][1];
-        Cf[2][1] = F[0][2] * F[1][0] - F[0][0] * F[1][2];
-        Cf[2][2] = F[0][0] * F[1][1] - F[0][1] * F[1][0];
+        Cf[1][0] = nl_dop(F[0][2], F[2][1], F[0][1], F[2][2]);
+        Cf[1][1] = nl_dop(F[0][0], F[2][2], F[0][2], F[2][0]);
+        Cf[1][2] = nl_dop(F[0][1], F[2][0], F[0][0], F[2][1]);
+        Cf[2][0] = nl_dop(F[0][1], F[1][2], F[0][2], F[1][1]);
+        Cf[2][1] = nl_dop(F[0][2], F[1][0], F[0][0], F[1][2]);
+        Cf[2][2] = nl_dop(F[0][0], F[1][1], F[0][1], F[1][0]);
         const double lnJ = log(J);
         // h_a = F^-T g_a = (cofactor matrix) g_a / J
         double h[4][3];

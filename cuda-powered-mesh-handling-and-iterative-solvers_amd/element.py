@@ -910,10 +910,10 @@ def compute_c3d4_deformation_gradient(coords, elements, displacement, device="cu
             "fem_tet4_geom")
     _raise_if_singular(bad, M)
     Fm = torch.eye(3, dtype=F64, device=dev) + torch.einsum("mai,maj->mij", u[elements], grads)
-    det = (Fm[:, 0, 0] * (Fm[:, 1, 1] * Fm[:, 2, 2] - Fm[:, 1, 2] * Fm[:, 2, 1])
-           + Fm[:, 0, 1] * (Fm[:, 1, 2] * Fm[:, 2, 0] - Fm[:, 1, 0] * Fm[:, 2, 2])
-           + Fm[:, 0, 2] * (Fm[:, 1, 0] * Fm[:, 2, 1] - Fm[:, 1, 1] * Fm[:, 2, 0]))
-    return _out(Fm, device, dtype), _out(det, device, dtype)
+    # det F as fem_tet4_nl forms it (compensated cofactors: accurate where F's entries are far above its determinant);
+    # the material does not enter it
+    out, _ = _tet4_nl(coords, elements, u, 1.0, 0.0, "svk", device, ("detF",), check=False)
+    return _out(Fm, device, dtype), _out(out["detF"], device, dtype)
 
 
 # ============================================================================ elastoplastic c3d4 (csrc/plasticity.hip)

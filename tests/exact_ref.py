@@ -378,6 +378,19 @@ def _transform(c, case):
     raise KeyError(case)
 
 
+def linear_map(case):
+    """The 3 x 3 matrix L of `_transform`: transformed = c @ L.T (+ the shift). Fields that must not depend on the
+    absolute coordinates are defined on the unit mesh and pushed through L (u @ L.T)."""
+    if case in ("plain", "flipped", "unflipped") or case.startswith("shift"):
+        return torch.eye(3, dtype=F64)
+    if case.startswith("scale"):
+        return float(case[5:]) * torch.eye(3, dtype=F64)
+    if case.startswith("squash"):
+        L = torch.diag(torch.tensor([1.0, 1.0, 1e-4], dtype=F64))
+        return _orthogonal() @ L if case.endswith("_rot") else L
+    raise KeyError(case)
+
+
 @functools.lru_cache(maxsize=None)
 def tet4_case(case):
     """(coords [64, 3], tets [162, 4]): kuhn_cube(3, jitter 0.15), every second element's local order [1, 0, 2, 3]

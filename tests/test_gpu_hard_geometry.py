@@ -17,7 +17,8 @@ element; two CPU orderings differ by < 1.5 x.
 
 Fixed assertions: mass matrices are bit-identical between a mesh and its mirrored copy; the isoparametric stiffness
 takes the sign of detJ (c3d6 single=True, B^T D B times an absolute volume, stays positive); a mesh with min|det| =
-4e-12 is accepted by every c3d4 path and one tet of |det| = 2.5e-13 inside it makes every path raise.
+4e-12 is accepted by every c3d4 path and one tet of |det| = 2.5e-13 inside it makes every path raise (the geometric
+stiffness and the body force document another rule, which is asserted as documented).
 
 Measured on the MI355X, as "error / ratio": the kernel's error against exact, and its ratio to max(calibration
 error, 2.2e-16) (the tests assert ratio <= 8; the largest is 2.11; the calibration side is CPU arithmetic and moves in
@@ -226,6 +227,7 @@ def test_tet4_mass_reordered_identical(gpu):
 
 def _tet4_paths(gpu):
     el, system = _mods()
+    from fem355 import loads
     u = lambda c: 1e-9 * torch.randn(c.shape[0], 3, dtype=F64, generator=torch.Generator().manual_seed(4))
     return {
         "K": lambda c, t: el.compute_c3d4_K_matrix(c, t, E, NU, device=gpu, dtype=F64),
@@ -240,6 +242,30 @@ def _tet4_paths(gpu):
         "stress": lambda c, t: el.compute_c3d4_element_stress(c, t, u(c), E, NU, device=gpu, dtype=F64),
         "oracle K": lambda c, t: R.tet4_K(c, t, E, NU),
         "oracle gradients": lambda c, t: R.tet4_gradients(c, t),
+        "svk tangent": lambda c, t: el.compute_c3d4_tangent_K_matrix(c, t, u(c), E, NU, "svk", device=gpu, dtype=F64),
+        "neo-Hooke tangent": lambda c, t: el.compute_c3d4_tangent_K_matrix(c, t, u(c), E, NU, "neo_hookean",
+                                                                           device=gpu, dtype=F64),
+        "J2 update": lambda c, t: el.compute_c3d4_plastic_update(c, t, u(c), E, NU, 1e-3 * E, 0.1 * E, device=gpu,
+                                                                 dtype=F64),
+        "thermal load": lambda c, t: loads.compute_thermal_load(c, t, "c3d4", E, NU, 1.2e-5, 50.0, device=gpu,
+                                                                dtype=F64),
+        "thermal stress": lambda c, t: loads.compute_thermal_element_stress(c, t, "c3d4", u(c), E, NU, 1.2e-5, 50.0,
+                                                                            device=gpu, dtype=F64),
+    }
+
+
+def _tet4_paths_other_rule(gpu):
+    """c3d4 paths that document a rule of their own for a degenerate element (asserted as documented): the geometric
+    stiffness flags only det = 0 or a non-finite det (csrc/buckling.hip), the body force needs |det| alone and
+    raises for no element (loads.py)."""
+    el, _ = _mods()
+    from fem355 import loads
+    u = lambda c: 1e-9 * torch.randn(c.shape[0], 3, dtype=F64, generator=torch.Generator().manual_seed(4))
+    return {
+        "geometric stiffness": lambda c, t: el.compute_geometric_stiffness(c, t, "c3d4", u(c), E, NU, device=gpu,
+                                                                           dtype=F64),
+        "body force": lambda c, t: loads.compute_body_force(c, t, "c3d4", RHO, [0.0, 0.0, -9.81], device=gpu,
+                                                            dtype=F64),
     }
 
 
@@ -248,15 +274,29 @@ def test_singular_threshold_accepts(gpu):
     c, t = X.threshold_case(False)
     for name, fn in _tet4_paths(gpu).items():
         fn(c, t)
+    for name, fn in _tet4_paths_other_rule(gpu).items():
+        assert bool(torch.isfinite(fn(c, t)).all()), name
 
 
 def test_singular_threshold_refuses(gpu):
-    """The same mesh with one tet of |det| = 2.5e-13 at element index 140: every path raises."""
+    """The same mesh with one tet of |det| = 2.5e-13 at element index 140: every path raises, except the two that
+    document another rule."""
     c, t = X.threshold_case(True)
     for name, fn in _tet4_paths(gpu).items():
         with pytest.raises(ValueError, match="Singular"):
             fn(c, t)
             pytest.fail(f"{name} accepted a singular element")
+    # the documented other rules: |det| = 2.5e-13 is neither zero nor non-finite, so both accept it with finite
+    # output; with the inserted tet collapsed to one point (det = 0) the geometric stiffness raises, and the body
+    # force, whose |det| / 6 is then zero, still does not
+    other = _tet4_paths_other_rule(gpu)
+    for name, fn in other.items():
+        assert bool(torch.isfinite(fn(c, t)).all()), name
+    c = c.clone()
+    c[-4:] = c[-4]
+    with pytest.raises(ValueError, match="Singular"):
+        other["geometric stiffness"](c, t)
+    assert bool(torch.isfinite(other["body force"](c, t)).all())
 
 
 # ----------------------------------------------------------------------------- isoparametric families
