@@ -228,6 +228,14 @@ SIGNATURES = {
     "fem_tet4_stress_thermal": (_I, [_P, _P, _L, _P, _D, _D, _D, _P, _I, _D, _P, _P, _P, _P]),
     "fem_iso_stress_thermal": (_I, [_P, _P, _L, _I, _P, _D, _D, _D, _P, _I, _D, _P, _P, _P, _I, _I, _P, _P, _P]),
     "fem_geo_scalar": (_I, [_P, _P, _L, _I, _P, _D, _D, _P, _P, _P, _I, _P, _P, _P]),
+    "fem_assemble_tet4_scaled": (_I, [_P, _P, _D, _D, _I, _P, _P, _L, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "fem_assemble_tet4_scaled_sl": (_I, [_P, _P, _D, _D, _I, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "fem_topopt_work_len": (_L, [_L]),
+    "fem_tet4_volumes": (_I, [_P, _P, _L, _P, _P, _L, _P, _P, _P, _P]),
+    "fem_tet4_unit_energy": (_I, [_P, _P, _L, _P, _D, _P, _D, _D, _D, _P, _P, _P, _P, _P, _P]),
+    "fem_simp_scale": (_I, [_P, _L, _D, _D, _P, _P]),
+    "fem_density_filter": (_I, [_P, _L, _P, _P, _L, _P, _P, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P]),
+    "fem_oc_update": (_I, [_P, _P, _P, _P, _L, _D, _D, _D, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1412,7 +1412,10 @@ using AccEl = AccCfg<16, 8, 16, 16, 256, true, false>;
 // k_sell_sl_pattern, and in a slice-uniform slice (uoff[s] >= 0) the accumulators are indexed by the slice's delta
 // list (the column search looks up node - row in it), so a row's missing offsets hold zeros there; bs = 3: the
 // plane-paired layout A (sell_val_a). The same additions in the same order as the plain layout: only positions differ.
-template <int BS, class Cfg, bool STORE, bool SL = false>
+// SCALED: element e contributes scale[e] K_e (fem_assemble_tet4_scaled*): the factor is loaded with the item's other
+// per-element data and multiplied into V at staging, into nothing else -- every staged value is linear in V. Off by
+// default: the unscaled instantiations never name `scale` and compile to the code they had without the parameter.
+template <int BS, class Cfg, bool STORE, bool SL = false, bool SCALED = false>
 __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__ X, const int64_t* __restrict__ conn,
                                                       double E, double nu, const int32_t* __restrict__ inc_ptr,
                                                       const int32_t* __restrict__ inc, int64_t N,
@@ -1421,7 +1424,8 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                                                       const int64_t* __restrict__ slice_ptr,
                                                       double* __restrict__ vals, int64_t* __restrict__ bad,
                                                       int64_t ntiles, const int32_t* __restrict__ uoff = nullptr,
-                                                      const int16_t* __restrict__ ucol = nullptr) {
+                                                      const int16_t* __restrict__ ucol = nullptr,
+                                                      const double* __restrict__ scale = nullptr) {
     static_assert(!SL || BS == 3 || Cfg::R == 64, "solver layout, bs = 1: one slice per tile");
     constexpr int R = Cfg::R, J = Cfg::J, LPR = Cfg::LPR, AW = Cfg::W, SEG = Cfg::SEG;
     constexpr int B2 = BS * BS;
@@ -1570,6 +1574,8 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                     const int64_t e = ea >> 2;
                     const int a = ea & 3;
                     const int64_t* c = cncur;
+                    double se = 1.0;
+                    if constexpr (SCALED) se = scale[e];
                     const bool ulist = SL && uo >= 0;
                     const int cl = ulist ? 0 : rp_s[r] - seg0, cn = ulist ? W : rp_s[r + 1] - rp_s[r];
                     const int kshift = ulist ? (int)(r0 + r) : 0;   // list entries are deltas node - row
@@ -1622,7 +1628,8 @@ __global__ void __launch_bounds__(256) k_asm_tet4_acc(const double* __restrict__
                         det = tet4_grads_n(X, cncur, g);
                     }
                     if (c0 == 0 && fabs(det) < 1e-12) atomicMin((unsigned long long*)bad, (unsigned long long)e);
-                    const double V = fabs(det) / 6.0;
+                    double V = fabs(det) / 6.0;
+                    if constexpr (SCALED) V *= se;
                     if constexpr (BS == 1) {
 #pragma unroll
                         for (int bb = 0; bb < 4; ++bb) dat_s[bb][it0] = p1_value(g[a], g[bb], E, V);
@@ -2566,6 +2573,83 @@ int fem_assemble_tet4_sl(const double* coords, const int64_t* conn, double E, do
     FEM_LAUNCHED();
     return FEM_OK;
 }
+
+// scale[e] K_e: the accumulator kernel's SCALED instantiations, chosen as the unscaled launchers choose theirs. The row
+// kernels (FEM355_ASM_ROWS) have no scaled form and the variable is not read here.
+static int tet4_scaled_args(const char* what, int bs, int max_width, const double* scale) {
+    if (bs != 1 && bs != 3) {
+        set_error("%s: block size %d unsupported", what, bs);
+        return FEM_EARG;
+    }
+    if (!scale) {
+        set_error("%s: scale is required", what);
+        return FEM_EARG;
+    }
+    if (max_width >= ACC_MAX_COLS) {
+        set_error("%s: a row of %d columns exceeds the value kernel's %d", what, max_width, ACC_MAX_COLS - 1);
+        return FEM_EARG;
+    }
+    return FEM_OK;
+}
+
+#define ASC_LAUNCH(BS_, CFG_, ST_, SL_)                                                                             \
+    do {                                                                                                            \
+        const int64_t nt = cdiv(N, 64) * (64 / CFG_::R);                                                            \
+        hipLaunchKernelGGL((k_asm_tet4_acc<BS_, CFG_, ST_, SL_, true>), dim3((unsigned)(cdiv(nt, NXCD) * NXCD)),    \
+                           dim3(CFG_::R * CFG_::LPR), 0, st, coords, conn, E, nu, inc_ptr, inc, N, rowptr, colidx,   \
+                           slice_ptr, vals, bad_idx, nt, uoff, ucol, scale);                                         \
+    } while (0)
+#define ASC_PICK(SL_)                                                                                               \
+    do {                                                                                                            \
+        if (bs == 3) {                                                                                              \
+            if (store) ASC_LAUNCH(3, AccEl, true, SL_);                                                             \
+            else ASC_LAUNCH(3, AccEl, false, SL_);                                                                  \
+        } else if (max_width > 0 && max_width <= AccP1w16::W) {                                                     \
+            if (store) ASC_LAUNCH(1, AccP1w16, true, SL_);                                                          \
+            else ASC_LAUNCH(1, AccP1w16, false, SL_);                                                               \
+        } else {                                                                                                    \
+            if (store) ASC_LAUNCH(1, AccP1, true, SL_);                                                             \
+            else ASC_LAUNCH(1, AccP1, false, SL_);                                                                  \
+        }                                                                                                           \
+    } while (0)
+
+int fem_assemble_tet4_scaled(const double* coords, const int64_t* conn, double E, double nu, int bs,
+                             const int32_t* inc_ptr, const int32_t* inc, int64_t N, const int32_t* rowptr,
+                             const int32_t* colidx, const int64_t* csr2sell, const int64_t* slice_ptr, int store,
+                             int max_width, const double* scale, double* vals, int64_t* bad_idx,
+                             fem_stream_t stream) {
+    (void)csr2sell;
+    const int rc = tet4_scaled_args("fem_assemble_tet4_scaled", bs, max_width, scale);
+    if (rc != FEM_OK) return rc;
+    if (N <= 0) return FEM_OK;
+    hipStream_t st = S(stream);
+    const int32_t* uoff = nullptr;
+    const int16_t* ucol = nullptr;
+    ASC_PICK(false);
+    FEM_LAUNCHED();
+    return FEM_OK;
+}
+
+int fem_assemble_tet4_scaled_sl(const double* coords, const int64_t* conn, double E, double nu, int bs,
+                                const int32_t* inc_ptr, const int32_t* inc, int64_t N, const int32_t* rowptr,
+                                const int32_t* colidx, const int64_t* slice_ptr, const int32_t* uoff,
+                                const int16_t* ucol, int store, int max_width, const double* scale, double* svals,
+                                int64_t* bad_idx, fem_stream_t stream) {
+    const int rc = tet4_scaled_args("fem_assemble_tet4_scaled_sl", bs, max_width, scale);
+    if (rc != FEM_OK) return rc;
+    if (bs == 1 && (!uoff || !ucol)) {
+        set_error("fem_assemble_tet4_scaled_sl: the solver-layout pattern (fem_sell_sl_pattern) is required");
+        return FEM_EARG;
+    }
+    if (N <= 0) return FEM_OK;
+    hipStream_t st = S(stream);
+    double* vals = svals;
+    ASC_PICK(true);
+    FEM_LAUNCHED();
+    return FEM_OK;
+}
+#undef ASC_PICK
+#undef ASC_LAUNCH
 
 int fem_assemble_from_ke_sl(const double* Ke, const int64_t* conn, int npe, const int32_t* inc_ptr, const int32_t* inc,
                             int64_t N, const int32_t* rowptr, const int32_t* colidx, const int64_t* slice_ptr,

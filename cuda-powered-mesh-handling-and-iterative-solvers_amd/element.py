@@ -1049,6 +1049,51 @@ def compute_geometric_stiffness(coords, elements, element_type, displacement=Non
     return _out(Gs, device, dtype)
 
 
+# ============================================================================ topology optimisation (csrc/topopt.hip)
+def compute_c3d4_unit_energy(coords, elements, u, nu, device="cuda:0", dtype=torch.float64):
+    """ce [M] = u_e^T K_e(E = 1, nu) u_e = V_e (lam1 tr(eps)^2 + 2 mu1 eps:eps) of every c3d4 element at the
+    displacement u [N,3] (fem_tet4_unit_energy): twice the strain energy per unit modulus, the quantity
+    compliance sensitivities are made of. Raises the singular-element ValueError for a degenerate element."""
+    lib = C.lib()
+    dev, coords, elements = _prep(coords, elements, device)
+    M = elements.shape[0]
+    ud = _disp(u, dev, coords.shape[0])
+    ce = torch.empty(M, dtype=F64, device=dev)
+    bad = _bad_scalar(dev, M)
+    C.check(lib.fem_tet4_unit_energy(C.ptr(coords), C.ptr(elements), M, C.ptr(ud), float(nu), None, 1.0, 0.5, 1.0,
+                                     C.ptr(ce), None, None, None, C.ptr(bad), C.stream(dev)), "fem_tet4_unit_energy")
+    _raise_if_singular(bad, M)
+    return _out(ce, device, dtype)
+
+
+def density_filter(coords, elements, rho, passes=1, adjoint=False, device="cuda:0", dtype=torch.float64):
+    """The node-average density filter of a c3d4 mesh applied `passes` >= 0 times to the element vector rho [M]
+    (fem_density_filter). Forward: rho_n = (sum_{e at n} V_e rho_e) / (sum_{e at n} V_e), out_e = the
+    mean of rho_n over the element's nodes -- it keeps constants and sum_e V_e rho_e. adjoint=True: the transposed
+    operator (for the chain rule of an objective formed on the filtered density). passes = 0 is the identity."""
+    if int(passes) != passes or int(passes) < 0:
+        raise ValueError(f"density_filter: passes must be an integer >= 0, got {passes}")
+    lib = C.lib()
+    dev, coords, elements = _prep(coords, elements, device)
+    M, N = elements.shape[0], coords.shape[0]
+    if elements.dim() != 2 or elements.shape[1] != 4:
+        raise ValueError(f"density_filter: c3d4 connectivity [M, 4] expected, got {tuple(elements.shape)}")
+    x = rho.to(device=dev, dtype=F64).contiguous().view(-1)
+    if x.numel() != M:
+        raise ValueError(f"density_filter: rho must hold {M} values, got {x.numel()}")
+    inc_ptr, inc = cached_incidence(elements, N)
+    e = lambda n: torch.empty(max(n, 1), dtype=F64, device=dev)
+    V, Vn, nt, et, out = e(M), e(N), e(N), e(M), e(M)
+    C.check(lib.fem_tet4_volumes(C.ptr(coords), C.ptr(elements), M, C.ptr(inc_ptr), C.ptr(inc), N, C.ptr(V),
+                                 C.ptr(Vn), None, C.stream(dev)), "fem_tet4_volumes")
+    C.check(lib.fem_density_filter(C.ptr(elements), M, C.ptr(inc_ptr), C.ptr(inc), N, C.ptr(V), C.ptr(Vn), C.ptr(x),
+                                   int(passes), 1 if adjoint else 0, 1.0, 0.5, C.ptr(nt), C.ptr(et), C.ptr(out), None,
+                                   C.stream(dev)), "fem_density_filter")
+    return _out(out[:M], device, dtype)
+
+
+__all__ += ["compute_c3d4_unit_energy", "density_filter"]
+
 __all__ += ["geometric_integration_points", "compute_geometric_stiffness"]
 
 __all__ += [

@@ -325,7 +325,8 @@ def _static_with_shells(coords, force, fixed, c3d4, c3d6, c3d8, s3, s4, material
 
 # ============================================================================ fused mesh -> solution pipeline
 def solve_tet4(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, tol=1e-8, max_iter=10000, device="cuda:0",
-               rtol=None, reorder=None, operator="assembled", preconditioner="jacobi", n_aggregates=None):
+               rtol=None, reorder=None, operator="assembled", preconditioner="jacobi", n_aggregates=None,
+               modulus_scale=None):
     """Assembly + Jacobi-PCG straight from the mesh (the benchmark pipeline; no element matrices stored):
     c3d4 Poisson (dpn 1, kappa = E) or elasticity (dpn 3), Dirichlet zero on `fixed` nodes via zeros in the
     exact Jacobi M_inv, reference PCG semantics (absolute tol on sqrt(r.z); `rtol` scales it by sqrt(r0.z0)).
@@ -334,7 +335,11 @@ def solve_tet4(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, tol=1e
     preconditioner="two-level" (kind="elastic", operator="assembled" only): the Jacobi weights plus the rigid-body
     coarse correction over `n_aggregates` aggregates (SellMatrix.rigid_coarse_space / pcg_two_level; sqrt(r.z) is then
     measured with the two-level z).
+    modulus_scale: a float64 device tensor [M] -- element e has the stiffness modulus_scale[e] K_e(E, nu) (a
+    heterogeneous Young's modulus, or conductivity for kind="poisson"; operator="assembled" only).
     Returns (u [N, dpn], PcgResult, SellMatrix)."""
+    if modulus_scale is not None and operator == "matfree":
+        raise ValueError("modulus_scale needs operator='assembled': the matrix-free operator has no per-element scale")
     if preconditioner not in ("jacobi", "two-level"):
         raise ValueError(f"unknown preconditioner {preconditioner!r} (supported: 'jacobi', 'two-level')")
     if preconditioner == "two-level" and (kind != "elastic" or operator != "assembled"):
@@ -355,8 +360,12 @@ def solve_tet4(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, tol=1e
         perm, inv = _sys.rcm_order(elements, N)
         coords, elements = _sys.renumber(coords, elements, perm, inv)
         fixed_mask, b = fixed_mask[perm], b[perm]
+    if modulus_scale is not None:   # element order is untouched by a node renumbering
+        modulus_scale = _sys.check_element_scale("solve_tet4", modulus_scale, elements.shape[0], dev)
     if operator == "matfree":
         A = _sys.MatFreeOperator(coords, elements, kind, E, nu)
+    elif modulus_scale is not None:
+        A = _sys.assemble_tet4_system(coords, elements, kind, E, nu, scale=modulus_scale)
     else:
         A = _sys.assemble_tet4_system(coords, elements, kind, E, nu)
     A.check_singular()
@@ -1215,6 +1224,93 @@ def elastoplastic_static_solver(coords, elements, F, fixed, E, nu, yield_stress,
         ns.close()
     res.u = res.u.view(N, 3).to(device=torch.device(device), dtype=dtype)
     return (res.u, res) if return_info else res.u
+
+
+# ============================================================================ topology optimisation
+# Density-based (SIMP) compliance minimisation on c3d4 meshes with an optimality-criteria update: the design loop of
+# system.TopOpt (csrc/topopt.hip and the scaled assembly). No counterpart in the reference.
+def topology_optimization_solver(coords, elements, F, fixed, E, nu, volume_fraction, penal=3.0, s_min=1e-3,
+                                 rho_min=1e-3, filter_passes=1, move=0.2, max_iter=100, change_tol=1e-2,
+                                 linear_rtol=1e-8, linear_max_iter=10000, rho0=None, passive=None, callback=None,
+                                 device="cuda:0"):
+    """Minimise the compliance F.u of a c3d4 mesh over the element densities rho in [rho_min, 1] at the volume
+    sum_e V_e rho_e = volume_fraction sum_e V_e. Per design iteration: rho_t = the node-average filter applied
+    filter_passes times, s = s_min + (1 - s_min) rho_t^penal, K(s) = sum_e s_e K_e(E, nu) refilled in place, K u = F by
+    Jacobi-PCG from the previous u to sqrt(r.z) <= linear_rtol sqrt(F.w F), dc = filter^T (-penal (1 - s_min)
+    rho_t^(penal-1) E ce), and the optimality-criteria update rho_e <- clamp(rho_e sqrt(-dc_e / (V_e l))) within the
+    move limit, its multiplier l found by 60 bisection steps on the device. Starts from rho = volume_fraction (or
+    rho0 [M]); stops at max |rho_new - rho| <= change_tol or after max_iter iterations (status MAX_ITER).
+    fixed: node ids, or a bool / uint8 [N,3] mask of single dofs held at zero. passive: int8 [M], 0 free, 1 solid
+    (pinned to 1), -1 void (pinned to rho_min). callback(iteration, record): called after every design iteration with
+    system.TopOpt.step's record. A linear solve that does not converge ends the run with the last accepted density
+    and status LINEAR_SOLVE_FAILED (no exception).
+    Limits: c3d4, one load case, compliance under one volume constraint, the node-average filter, Jacobi-PCG on the
+    assembled operator, one GPU. Not built: radius or Helmholtz filters, projection, MMA, stress or several
+    constraints, other element types, per-element nu, the scale in the matrix-free operator, the two-level
+    preconditioner inside the loop, multi-GPU.
+    Returns a system.TopOptResult (tensors on `device`)."""
+    what = "topology_optimization_solver"
+    _sys.check_topopt_parameters(what, volume_fraction, penal, s_min, rho_min, move, filter_passes)
+    if not torch.is_tensor(coords) or coords.dim() != 2 or coords.shape[1] != 3:
+        raise ValueError(f"{what}: coords must be [N, 3], got {tuple(getattr(coords, 'shape', ()))}")
+    N = coords.shape[0]
+    if not torch.is_tensor(elements) or elements.dim() != 2 or elements.shape[1] != 4:
+        raise ValueError(f"{what}: c3d4 connectivity [M, 4] expected, got {tuple(getattr(elements, 'shape', ()))}")
+    M = elements.shape[0]
+    if elements.numel() and (int(elements.min()) < 0 or _max_node(elements) > N):
+        raise ValueError(f"{what}: the mesh references a node outside [0, {N})")
+    if not torch.is_tensor(F) or tuple(F.shape) != (N, 3):
+        raise ValueError(f"{what}: F must be [{N}, 3], got {tuple(getattr(F, 'shape', ()))}")
+    if int(max_iter) < 1 or int(linear_max_iter) < 1:
+        raise ValueError(f"{what}: max_iter and linear_max_iter must be >= 1")
+    if not float(change_tol) >= 0.0 or not float(linear_rtol) > 0.0:
+        raise ValueError(f"{what}: change_tol must be >= 0 and linear_rtol > 0")
+    if rho0 is not None and (not torch.is_tensor(rho0) or rho0.numel() != M):
+        raise ValueError(f"{what}: rho0 must hold {M} values")
+    if passive is not None and (not torch.is_tensor(passive) or passive.numel() != M):
+        raise ValueError(f"{what}: passive must hold {M} values")
+    mask = _fixed_mask(what, fixed, N)
+    if not bool((F.detach().to("cpu", F64)[~mask] != 0).any()):
+        raise ValueError(f"{what}: the load is zero on the free dofs")
+    dev = _dev(device)
+    coords = coords.to(device=dev, dtype=F64).contiguous()
+    el = elements.to(device=dev, dtype=LONG).contiguous()
+    rho = (torch.full((M,), float(volume_fraction), dtype=F64, device=dev) if rho0 is None
+           else rho0.to(device=dev, dtype=F64).reshape(-1).clone())
+    to = _sys.TopOpt(coords, el, F, mask.to(device=dev, dtype=torch.uint8).view(-1), E, nu, volume_fraction, penal,
+                     s_min, rho_min, filter_passes, move, passive=passive, graph=cached_graph(el, N))
+    res = _sys.TopOptResult(rho, None, None, None, False, _sys.TOPOPT_MAX_ITER, "", [], [], [], [], [])
+    try:
+        for k in range(1, int(max_iter) + 1):
+            rec = to.step(rho, linear_rtol, linear_max_iter)
+            res.filtered_density, res.modulus_scale, res.u = rec["rho_t"].clone(), rec["s"].clone(), \
+                rec["u"].view(N, 3).clone()
+            res.pcg_iterations.append(rec["pcg_iterations"])
+            if rec["rho_new"] is None:
+                res.status = _sys.TOPOPT_LINEAR_SOLVE_FAILED
+                res.message = (f"The linear solve of design iteration {k} did not converge within "
+                               f"{int(linear_max_iter)} iterations (PCG status {rec['status']}).")
+                break
+            res.compliance.append(rec["compliance"])
+            res.load_work.append(rec["load_work"])
+            res.volume_fraction.append(rec["volume_fraction"])
+            res.change.append(rec["change"])
+            rho = rec["rho_new"].clone()
+            res.density = rho
+            if callback is not None:
+                callback(k, rec)
+            if rec["change"] <= float(change_tol):
+                res.converged, res.status = True, _sys.TOPOPT_OK
+                break
+        else:
+            res.message = f"The design did not settle within {int(max_iter)} iterations."
+    finally:
+        to.close()
+    out = torch.device(device)
+    res.density = res.density.to(out)
+    for name in ("filtered_density", "modulus_scale", "u"):
+        setattr(res, name, getattr(res, name).to(out))
+    return res
 
 
 def newton_raphson_solver(K_func, elements, F_ext, u_init=None, tol=1e-8, max_iter=50, device="cuda:0",

@@ -622,6 +622,20 @@ class CoarseSpace:
         return (0.5 * (Einv + Einv.T)).contiguous(), 6 * k - mk
 
 
+def check_element_scale(what, scale, M, device):
+    """The per-element scale of the scaled assembly: a float64 tensor of M values on `device`, else ValueError (a host
+    tensor never reaches C.ptr). Returns it flat and contiguous."""
+    if not torch.is_tensor(scale):
+        raise ValueError(f"{what}: scale must be a float64 device tensor of {M} values, got {type(scale).__name__}")
+    if not scale.is_cuda or scale.device != torch.device(device):
+        raise ValueError(f"{what}: scale must live on {device}, got a {scale.device} tensor")
+    if scale.dtype != F64:
+        raise ValueError(f"{what}: scale must be float64, got {scale.dtype}")
+    if scale.numel() != int(M):
+        raise ValueError(f"{what}: scale must hold one value per element ({M}), got {scale.numel()}")
+    return scale.contiguous().view(-1)
+
+
 @_scoped
 class SellMatrix:
     """Assembled global operator in SELL-64 with bs x bs blocks (bs = dofs per node)."""
@@ -827,8 +841,12 @@ class SellMatrix:
                                              C.ptr(out), C.stream(self.device)), "fem_assemble_from_ke_sym")
         return self
 
-    def add_tet4(self, coords: torch.Tensor, elements: torch.Tensor, E: float, nu: float = 0.0):
-        """vals += the c3d4 operator computed on the fly (bs=3: elasticity E, nu; bs=1: Poisson, kappa=E)."""
+    def add_tet4(self, coords: torch.Tensor, elements: torch.Tensor, E: float, nu: float = 0.0, scale=None):
+        """vals += the c3d4 operator computed on the fly (bs=3: elasticity E, nu; bs=1: Poisson, kappa=E).
+        scale: a float64 device tensor of one factor per element -- element e then contributes scale[e] K_e (the
+        per-element modulus of DESIGN §8t; fem_assemble_tet4_scaled*). None: the unscaled entry points."""
+        if scale is not None:
+            return self._add_tet4_scaled(coords, elements, E, nu, scale)
         lib = C.lib()
         bad = _dev_scalar(self.device, I64, elements.shape[0])
         self._bad = (bad, elements.shape[0])
@@ -856,6 +874,38 @@ class SellMatrix:
                                           C.ptr(self.g.slice_ptr), 1 if store else 0, self.g.max_width,
                                           C.ptr(self._vals), C.ptr(bad), C.stream(self.device)),
                 "fem_assemble_tet4_ex2")
+        return self
+
+    def _add_tet4_scaled(self, coords, elements, E, nu, scale):
+        """add_tet4 with a per-element scale: the same layout choice, store handling and `bad` bookkeeping, through
+        the scaled entry points (which have no row-kernel form: FEM355_ASM_ROWS is not consulted)."""
+        scale = check_element_scale("add_tet4", scale, elements.shape[0], self.device)
+        lib = C.lib()
+        bad = _dev_scalar(self.device, I64, elements.shape[0])
+        self._bad = (bad, elements.shape[0])
+        if self._sl_target():
+            sl = self.g.solver_layout() if self.bs == 1 else None
+            store = self._fresh
+            self._fresh = False
+            C.check(lib.fem_assemble_tet4_scaled_sl(C.ptr(coords), C.ptr(elements), float(E), float(nu), self.bs,
+                                                    C.ptr(self.g.inc_ptr), C.ptr(self.g.inc), self.g.n_nodes,
+                                                    C.ptr(self.g.rowptr), C.ptr(self.g.colidx),
+                                                    C.ptr(self.g.slice_ptr), C.ptr(sl.uoff) if sl else None,
+                                                    C.ptr(sl.ucol) if sl else None, 1 if store else 0,
+                                                    self.g.max_width, C.ptr(scale), C.ptr(self._svals_buf()),
+                                                    C.ptr(bad), C.stream(self.device)), "fem_assemble_tet4_scaled_sl")
+            self._sl_ok, self._plain_ok = True, False
+            return self
+        self._modify_plain()
+        store = self._fresh
+        self._fresh = False
+        self._plain_ok = True
+        C.check(lib.fem_assemble_tet4_scaled(C.ptr(coords), C.ptr(elements), float(E), float(nu), self.bs,
+                                             C.ptr(self.g.inc_ptr), C.ptr(self.g.inc), self.g.n_nodes,
+                                             C.ptr(self.g.rowptr), C.ptr(self.g.colidx), None,
+                                             C.ptr(self.g.slice_ptr), 1 if store else 0, self.g.max_width,
+                                             C.ptr(scale), C.ptr(self._vals), C.ptr(bad), C.stream(self.device)),
+                "fem_assemble_tet4_scaled")
         return self
 
     def check_singular(self):
@@ -2379,15 +2429,234 @@ class PlasticStatics(NewtonStatics):
         return out[: self.M]
 
 
-def assemble_tet4_system(coords, elements, kind="poisson", E=1.0, nu=0.0, graph=None):
+def assemble_tet4_system(coords, elements, kind="poisson", E=1.0, nu=0.0, graph=None, scale=None):
     """Mesh -> assembled device operator in one pass (pattern + values; element matrices never stored).
-    kind: "poisson" (bs=1, kappa=E) or "elastic" (bs=3)."""
+    kind: "poisson" (bs=1, kappa=E) or "elastic" (bs=3). scale: per-element factors on K_e (SellMatrix.add_tet4)."""
     n_nodes = coords.shape[0]
     bs = 1 if kind == "poisson" else 3
+    if scale is not None:
+        scale = check_element_scale("assemble_tet4_system", scale, elements.shape[0], coords.device)
     # bs = 1: the solver layout formed in the pattern's fill pass (the value kernel writes it straight away)
     g = graph if graph is not None else build_graph(elements, n_nodes, solver_layout=bs == 1)
-    A = SellMatrix(g, bs).add_tet4(coords.to(F64).contiguous(), elements.contiguous(), E, nu)
+    A = SellMatrix(g, bs).add_tet4(coords.to(F64).contiguous(), elements.contiguous(), E, nu, scale=scale)
     return A
+
+
+# ============================================================================ topology optimisation (csrc/topopt.hip)
+TOPOPT_OK, TOPOPT_MAX_ITER, TOPOPT_LINEAR_SOLVE_FAILED = "OK", "MAX_ITER", "LINEAR_SOLVE_FAILED"
+OC_BISECTIONS = 60
+
+
+@dataclass
+class TopOptResult:
+    """Outcome of solver.topology_optimization_solver. density is the last accepted design (the optimiser's variable),
+    filtered_density / modulus_scale / u belong to the last design that was solved; the lists have one entry per design
+    iteration that finished its linear solve (volume_fraction and change: per update)."""
+    density: torch.Tensor
+    filtered_density: torch.Tensor
+    modulus_scale: torch.Tensor
+    u: torch.Tensor
+    converged: bool
+    status: str                      # TOPOPT_OK / TOPOPT_MAX_ITER / TOPOPT_LINEAR_SOLVE_FAILED
+    message: str = ""
+    compliance: list = None          # sum_e s_e E ce_e = u^T K(s) u
+    load_work: list = None           # F.u (equals the compliance up to the linear solve's error)
+    volume_fraction: list = None
+    change: list = None              # max |rho_new - rho|
+    pcg_iterations: list = None
+
+
+def check_topopt_parameters(what, volume_fraction, penal, s_min, rho_min, move, filter_passes):
+    """The parameter ValueErrors of the topology-optimisation entry points, before any device call."""
+    if not 0.0 < float(volume_fraction) <= 1.0:
+        raise ValueError(f"{what}: volume_fraction must lie in (0, 1], got {volume_fraction}")
+    if not float(penal) >= 1.0:
+        raise ValueError(f"{what}: penal must be >= 1, got {penal}")
+    if not 0.0 < float(s_min) < 1.0:
+        raise ValueError(f"{what}: s_min must lie in (0, 1), got {s_min}")
+    if not 0.0 < float(rho_min) < 1.0:
+        raise ValueError(f"{what}: rho_min must lie in (0, 1), got {rho_min}")
+    if not float(move) > 0.0:
+        raise ValueError(f"{what}: move must be > 0, got {move}")
+    if int(filter_passes) != filter_passes or int(filter_passes) < 0:
+        raise ValueError(f"{what}: filter_passes must be an integer >= 0, got {filter_passes}")
+
+
+@_scoped
+class TopOpt:
+    """Device state of a SIMP compliance minimisation on a c3d4 mesh, allocated once: the graph, one bs = 3
+    SellMatrix refilled every design iteration by reset() + add_tet4(..., scale=s), the element volumes V and node
+    volumes Vn, every element / node work buffer, b / x / w and ONE PCG context over them (the create / attach_cols16 /
+    attach_layout / set_tol sequence of NewtonStatics.solve_increment). x is not zeroed between design iterations: each
+    solve starts from the previous displacement. fixed_mask: uint8 [3 N], 1 on the dofs held at zero. F: the load
+    [N,3]. passive: int8 [M] (0 free, 1 solid, -1 void) or None."""
+
+    def __init__(self, coords, elements, F, fixed_mask, E, nu, volume_fraction, penal=3.0, s_min=1e-3, rho_min=1e-3,
+                 filter_passes=1, move=0.2, passive=None, graph: Graph = None):
+        check_topopt_parameters("TopOpt", volume_fraction, penal, s_min, rho_min, move, filter_passes)
+        self.lib = C.lib()
+        self.device = dev = coords.device
+        self.coords = coords.to(F64).contiguous()
+        self.elements = elements.to(I64).contiguous()
+        if self.elements.dim() != 2 or self.elements.shape[1] != 4:
+            raise ValueError(f"TopOpt: c3d4 connectivity [M, 4] expected, got {tuple(self.elements.shape)}")
+        self.E, self.nu = float(E), float(nu)
+        self.volfrac, self.penal, self.s_min, self.rho_min = float(volume_fraction), float(penal), float(s_min), \
+            float(rho_min)
+        self.passes, self.move = int(filter_passes), float(move)
+        self.N, self.M = self.coords.shape[0], self.elements.shape[0]
+        n, m = 3 * self.N, max(self.M, 1)
+        self.mask = fixed_mask.to(device=dev, dtype=torch.uint8).contiguous().view(-1)
+        if self.mask.numel() != n:
+            raise ValueError(f"TopOpt: fixed_mask must hold {n} values, got {self.mask.numel()}")
+        self.passive = None
+        if passive is not None:
+            if not torch.is_tensor(passive) or passive.numel() != self.M:
+                raise ValueError(f"TopOpt: passive must hold {self.M} values")
+            self.passive = passive.to(device=dev, dtype=torch.int8).contiguous().view(-1)
+        self.g = graph if graph is not None else build_graph(self.elements, self.N)
+        self.A = SellMatrix(self.g, 3)
+        e = lambda *s: torch.empty(s, dtype=F64, device=dev)
+        self.V, self.Vn = e(m), e(max(self.N, 1))
+        self.node_tmp, self.elem_tmp = e(max(self.N, 1)), e(m)
+        self.rho_t, self.s, self.ce, self.dct, self.dc, self.rho_new = e(m), e(m), e(m), e(m), e(m), e(m)
+        self.work = e(max(int(self.lib.fem_topopt_work_len(self.M)), 1))
+        self.out = e(4)                                    # compliance | change, volume fraction | spare
+        self.idx = torch.empty(1, dtype=I64, device=dev)   # lowest degenerate element of a launch
+        self.b, self.x, self.w = e(n), torch.zeros(n, dtype=F64, device=dev), e(n)
+        self.b.copy_(F.to(device=dev, dtype=F64).reshape(-1))
+        self.h = ctypes.c_void_p()
+        self._stream = C.stream(dev)
+        self.idx.fill_(self.M)
+        C.check(self.lib.fem_tet4_volumes(C.ptr(self.coords), C.ptr(self.elements), self.M, C.ptr(self.g.inc_ptr),
+                                          C.ptr(self.g.inc), self.N, C.ptr(self.V), C.ptr(self.Vn), C.ptr(self.idx),
+                                          self._stream), "fem_tet4_volumes")
+        if int(self.idx.item()) < self.M:
+            raise ValueError("Singular matrix encountered while computing B matrix.")
+
+    def _elem(self, x, what):
+        x = x.to(device=self.device, dtype=F64).contiguous().view(-1)
+        if x.numel() != self.M:
+            raise ValueError(f"TopOpt: {what} must hold {self.M} values, got {x.numel()}")
+        return x
+
+    def _filter(self, x, out, adjoint, scale=None):
+        C.check(self.lib.fem_density_filter(C.ptr(self.elements), self.M, C.ptr(self.g.inc_ptr), C.ptr(self.g.inc),
+                                            self.N, C.ptr(self.V), C.ptr(self.Vn), C.ptr(x), self.passes,
+                                            1 if adjoint else 0, self.penal, self.s_min, C.ptr(self.node_tmp),
+                                            C.ptr(self.elem_tmp), C.ptr(out), C.ptr(scale), self._stream),
+                "fem_density_filter")
+        return out
+
+    def filter(self, rho):
+        """rho_t = the density filter applied filter_passes times (this object's buffer)."""
+        return self._filter(self._elem(rho, "rho"), self.rho_t, False)[: self.M]
+
+    def filter_adjoint(self, g):
+        """The transposed filter of an element vector (this object's dc buffer)."""
+        return self._filter(self._elem(g, "g"), self.dc, True)[: self.M]
+
+    def scale(self, rho):
+        """(rho_t, s): the filtered density and the modulus scale s = s_min + (1 - s_min) rho_t^penal, in one call
+        (the scale is fused into the filter's last element kernel). Both are this object's buffers."""
+        self._filter(self._elem(rho, "rho"), self.rho_t, False, scale=self.s)
+        return self.rho_t[: self.M], self.s[: self.M]
+
+    def solve(self, s, linear_rtol=1e-8, linear_max_iter=10000, chunk=32):
+        """K(s) u = F on the free dofs by Jacobi-PCG from the previous u (this object's x, zero at first), stopped at
+        sqrt(r.z) <= linear_rtol sqrt(F.w F) -> (u, PCG iterations, status). u is this object's buffer."""
+        A = self.A
+        A.reset()
+        if self.M:
+            A.add_tet4(self.coords, self.elements, self.E, self.nu, scale=self._elem(s, "s"))
+        else:
+            A.plain_values()
+        self.w.copy_(A.jacobi(self.mask))   # (a degenerate element was refused when the volumes were formed)
+        bn = float(torch.sqrt(torch.dot(self.b, self.w * self.b)))
+        if not bn > 0.0:
+            raise ValueError("TopOpt: the load is zero on the free dofs")
+        if not self.h:
+            plain = _schedule(False, None, 3) == SCHED_FUSED
+            C.check(self.lib.fem_pcg_create(A.g.n_nodes, 3, C.ptr(A.g.slice_ptr), C.ptr(A.g.cols),
+                                            A.solver_vals_ptr(plain), C.ptr(self.b), C.ptr(self.x), C.ptr(self.w),
+                                            C.MODE_PCG, 0.0, 1e-30, None, 0, self._stream, ctypes.byref(self.h)),
+                    "fem_pcg_create")
+            C.check(self.lib.fem_pcg_set_schedule(self.h, _schedule(False, None, 3)), "fem_pcg_set_schedule")
+            C.check(self.lib.fem_pcg_set_entries(self.h, A.g.sell_entries), "fem_pcg_set_entries")
+            A.attach_cols16(self.h)
+            A.attach_layout(self.h, plain)
+            self._ctx_sl = A.solver_layout
+        elif self._ctx_sl != A.solver_layout:   # the refill must land where the context reads
+            raise C.FemError("TopOpt: the matrix changed layout under its solver context")
+        elif not self._ctx_sl:
+            A.plain_values()
+        C.check(self.lib.fem_pcg_set_tol(self.h, float(linear_rtol) * bn), "fem_pcg_set_tol")
+        it, stt, rz = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+        C.check(self.lib.fem_pcg_solve(self.h, int(linear_max_iter), int(chunk), ctypes.byref(it), ctypes.byref(stt),
+                                       ctypes.byref(rz)), "fem_pcg_solve")
+        _check_sync(stt.value)
+        return self.x, it.value, stt.value
+
+    def _energy(self, u, rho_t):
+        self.idx.fill_(self.M)
+        C.check(self.lib.fem_tet4_unit_energy(C.ptr(self.coords), C.ptr(self.elements), self.M, C.ptr(u), self.nu,
+                                              C.ptr(rho_t), self.penal, self.s_min, self.E, C.ptr(self.ce),
+                                              C.ptr(self.dct), C.ptr(self.work), C.ptr(self.out[0:1]),
+                                              C.ptr(self.idx), self._stream), "fem_tet4_unit_energy")
+        self._filter(self.dct, self.dc, True)
+
+    def sensitivities(self, u, rho_t):
+        """(dc, compliance): dc = F^T dct with dct[e] = -penal (1 - s_min) rho_t[e]^(penal - 1) E ce[e], the derivative
+        of the compliance u^T K(s) u in the design rho at fixed load; dc is this object's buffer."""
+        u = u.to(device=self.device, dtype=F64).contiguous().view(-1)
+        if u.numel() != 3 * self.N:
+            raise ValueError(f"TopOpt: u must hold {3 * self.N} values, got {u.numel()}")
+        self._energy(u, self._elem(rho_t, "rho_t"))
+        return self.dc[: self.M], float(self.out[0].item())
+
+    def _update(self, rho, dc):
+        C.check(self.lib.fem_oc_update(C.ptr(rho), C.ptr(dc), C.ptr(self.V), C.ptr(self.passive), self.M, self.volfrac,
+                                       self.move, self.rho_min, OC_BISECTIONS, C.ptr(self.work), C.ptr(self.rho_new),
+                                       C.ptr(self.out[1:3]), self._stream), "fem_oc_update")
+
+    def update(self, rho, dc):
+        """The optimality-criteria step -> (rho_new, max |rho_new - rho|, reached volume fraction); rho_new is this
+        object's buffer."""
+        self._update(self._elem(rho, "rho"), self._elem(dc, "dc"))
+        o = self.out[1:3].cpu()
+        return self.rho_new[: self.M], float(o[0]), float(o[1])
+
+    def step(self, rho, linear_rtol=1e-8, linear_max_iter=10000):
+        """One design iteration from rho: filter + scale, refill, solve, sensitivities, OC update, with ONE small
+        device-to-host copy after the solve's own -> dict(rho_new, rho_t, s, u, compliance, load_work, change,
+        volume_fraction, pcg_iterations, status). After a linear solve that did not converge nothing else is run and
+        rho_new is None."""
+        rho = self._elem(rho, "rho")
+        rho_t, s = self.scale(rho)
+        u, it, stt = self.solve(s, linear_rtol, linear_max_iter)
+        rec = {"rho_new": None, "rho_t": rho_t, "s": s, "u": u, "pcg_iterations": it, "status": stt}
+        if stt != C.PCG_CONVERGED:
+            return rec
+        self._energy(u, self.rho_t)
+        self._update(rho, self.dc)
+        self.out[3] = torch.dot(self.b, u)
+        o = torch.cat((self.out, self.idx.to(F64))).cpu()
+        if int(o[4]) < self.M:
+            raise ValueError("Singular matrix encountered while computing B matrix.")
+        rec.update(rho_new=self.rho_new[: self.M], compliance=float(o[0]), change=float(o[1]),
+                   volume_fraction=float(o[2]), load_work=float(o[3]))
+        return rec
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.fem_pcg_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def stream_ceiling(dev, gib=2.0, reps=5):

@@ -491,6 +491,23 @@ int fem_assemble_tet4_sl(const double* coords, const int64_t* conn, double E, do
                          const int32_t* inc_ptr, const int32_t* inc, int64_t N, const int32_t* rowptr,
                          const int32_t* colidx, const int64_t* slice_ptr, const int32_t* uoff, const int16_t* ucol,
                          int store, int max_width, double* svals, int64_t* bad_idx, fem_stream_t stream);
+/* Per-element modulus scale: the arguments of fem_assemble_tet4_ex2 / fem_assemble_tet4_sl plus scale [M]
+ * (device, fp64, required: NULL is FEM_EARG). Element e contributes scale[e] K_e(E, nu) (bs = 3) or
+ * scale[e] K_e(kappa = E) (bs = 1): the factor multiplies the element volume when an item is staged and nothing else,
+ * so scale = 1 gives the unscaled entry point's bits and a power-of-two scale that power of two times them. The same
+ * kernel configurations, store handling, layouts and bad_idx as the unscaled calls; scale is only read and may not
+ * alias vals / svals. csr2sell is unused (nullable): the row kernels (FEM355_ASM_ROWS) have no scaled form and that
+ * variable is ignored here. */
+int fem_assemble_tet4_scaled(const double* coords, const int64_t* conn, double E, double nu, int bs,
+                             const int32_t* inc_ptr, const int32_t* inc, int64_t N, const int32_t* rowptr,
+                             const int32_t* colidx, const int64_t* csr2sell, const int64_t* slice_ptr, int store,
+                             int max_width, const double* scale, double* vals, int64_t* bad_idx,
+                             fem_stream_t stream);
+int fem_assemble_tet4_scaled_sl(const double* coords, const int64_t* conn, double E, double nu, int bs,
+                                const int32_t* inc_ptr, const int32_t* inc, int64_t N, const int32_t* rowptr,
+                                const int32_t* colidx, const int64_t* slice_ptr, const int32_t* uoff,
+                                const int16_t* ucol, int store, int max_width, const double* scale, double* svals,
+                                int64_t* bad_idx, fem_stream_t stream);
 int fem_assemble_from_ke_sl(const double* Ke, const int64_t* conn, int npe, const int32_t* inc_ptr, const int32_t* inc,
                             int64_t N, const int32_t* rowptr, const int32_t* colidx, const int64_t* slice_ptr,
                             int store, int max_width, double* svals, fem_stream_t stream);
@@ -1069,6 +1086,49 @@ int fem_iso_stress_thermal(const double* coords, const int64_t* conn, int64_t M,
 int fem_geo_scalar(const double* coords, const int64_t* conn, int64_t M, int npe, const double* u, double E, double nu,
                    const double* sigma0, const double* dN, const double* w, int n_ip, double* Gs, uint8_t* bad,
                    fem_stream_t stream);
+
+/* ------------------------------------------------------------------ topology optimisation (csrc/topopt.hip)
+ * The design loop of density-based (SIMP) compliance minimisation on c3d4 around fem_assemble_tet4_scaled* and a PCG
+ * solve; the reference has no counterpart. All arrays device memory, fp64 unless noted; no atomics but the atomicMin of
+ * *bad_idx; every sum in a fixed order (the same bits on every run). V_e, g_a: volume and gradients of fem_tet4_geom;
+ * inc entries are 4 e + a (fem_incidence). Nothing past M elements / N nodes of any array is read or written.
+ * fem_topopt_work_len: doubles of workspace `work` that fem_tet4_unit_energy and fem_oc_update need for M elements.
+ * fem_tet4_volumes: V [M] = |det| / 6 and (Vn != NULL) Vn [N] = sum of V_e over the elements containing the node, in
+ *   incidence order (0 for a node without elements). *bad_idx (nullable, preset to M) as fem_tet4_ke.
+ * fem_tet4_unit_energy: ce [M] = u_e^T K_e(E = 1, nu) u_e = V_e (lam1 tr(eps)^2 + 2 mu1 eps:eps), eps = sym(sum_a u_a
+ *   (x) g_a), u [N,3]. With rho_t [M] (nullable) s_e = s_min + (1 - s_min) rho_t[e]^penal, else s_e = 1; dct [M]
+ *   (nullable, needs rho_t) = -penal (1 - s_min) rho_t[e]^(penal - 1) E0 ce[e]; *compliance (nullable, needs work) =
+ *   sum_e s_e E0 ce[e], per-block partials in work summed by one block in block order. A degenerate element
+ *   (|det| < 1e-12) writes zeros and lowers *bad_idx (required, preset to M). Outputs may not alias inputs.
+ * fem_simp_scale: s [M] = s_min + (1 - s_min) rho_t^penal; s may alias rho_t.
+ * fem_density_filter: the node-average filter applied `passes` >= 0 times (0: out = in, bit for bit).
+ *   forward (adjoint == 0): y[n] = (sum_{e containing n} V_e x_e) / Vn[n], out[e] = 1/4 sum_a y[e_a] -- keeps constants
+ *     and the volume sum_e V_e x_e; scale [M] (nullable) also receives fem_simp_scale(out) from the last pass;
+ *   adjoint: y[n] = (1/4 sum_{e containing n} x_e) / Vn[n], out[e] = V_e sum_a y[e_a]; scale must be NULL.
+ *   node_tmp [N] (passes > 0) and elem_tmp [M] (passes > 1) are overwritten. out may alias in; in is otherwise
+ *   untouched. V / Vn from fem_tet4_volumes.
+ * fem_oc_update: the optimality-criteria update with its bisection on the device (no copy to the host, no grid
+ *   barrier). b_e = max(0, -dc_e) / V_e, lo_e = max(rho_min, rho_e - move), hi_e = min(1, rho_e + move),
+ *   rho_new_e(l) = min(hi_e, max(lo_e, rho_e sqrt(b_e / l))). passive [M] (int8, nullable): 0 free, 1 solid (pinned to
+ *   1), -1 void (pinned to rho_min); passive elements count in the volume and not in the bracket. Bracket
+ *   [rho_min^2 min_{b_e > 0} b_e, max b_e / rho_min^2]; n_bisect steps at l_mid = sqrt(l_lo) sqrt(l_hi): sum_e V_e
+ *   rho_new_e(l_mid) > volfrac sum_e V_e moves l_lo up, else l_hi down; rho_new [M] is taken at l_hi. No free b_e > 0:
+ *   rho_new = rho. out [2] = (max_e |rho_new_e - rho_e|, sum_e V_e rho_new_e / sum_e V_e). rho_new may alias rho;
+ *   rho, dc, V, passive are otherwise untouched; work is overwritten. */
+int64_t fem_topopt_work_len(int64_t M);
+int fem_tet4_volumes(const double* coords, const int64_t* conn, int64_t M, const int32_t* inc_ptr, const int32_t* inc,
+                     int64_t N, double* V, double* Vn, int64_t* bad_idx, fem_stream_t stream);
+int fem_tet4_unit_energy(const double* coords, const int64_t* conn, int64_t M, const double* u, double nu,
+                         const double* rho_t, double penal, double s_min, double E0, double* ce, double* dct,
+                         double* work, double* compliance, int64_t* bad_idx, fem_stream_t stream);
+int fem_simp_scale(const double* rho_t, int64_t M, double penal, double s_min, double* s, fem_stream_t stream);
+int fem_density_filter(const int64_t* conn, int64_t M, const int32_t* inc_ptr, const int32_t* inc, int64_t N,
+                       const double* V, const double* Vn, const double* in, int passes, int adjoint, double penal,
+                       double s_min, double* node_tmp, double* elem_tmp, double* out, double* scale,
+                       fem_stream_t stream);
+int fem_oc_update(const double* rho, const double* dc, const double* V, const int8_t* passive, int64_t M,
+                  double volfrac, double move, double rho_min, int n_bisect, double* work, double* rho_new,
+                  double* out, fem_stream_t stream);
 
 #ifdef __cplusplus
 }
