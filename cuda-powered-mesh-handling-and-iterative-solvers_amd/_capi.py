@@ -35,6 +35,8 @@ ISO_SUM, ISO_STACK, ISO_VOLUME, ISO_MASS = 0, 1, 2, 3
 MASS_SELL, MASS_DIAG = 0, 1   # include/fem355.h fem_mass_form
 MAT_SVK, MAT_NEO_HOOKEAN = 0, 1   # include/fem355.h FEM_MAT_*
 MATERIALS = {"svk": MAT_SVK, "neo_hookean": MAT_NEO_HOOKEAN}
+MAT_LINEAR = 2
+EXPLICIT_MATERIALS = {"linear": MAT_LINEAR, **MATERIALS}   # explicit dynamics (fem_xd_*) also steps the linear operator
 SHELL_LOCAL, SHELL_POINTS, SHELL_GLOBAL = 0, 1, 2   # include/fem355.h FEM_SHELL_*
 LOAD_NONE, LOAD_UNIFORM, LOAD_NODAL, LOAD_ELEMENT = 0, 1, 2, 3   # include/fem355.h FEM_LOAD_*
 MODAL_OUT_GM, MODAL_OUT_NORMS, MODAL_OUT_LEN = 576, 1152, 1168   # include/fem355.h FEM_MODAL_OUT_*
@@ -236,6 +238,15 @@ SIGNATURES = {
     "fem_simp_scale": (_I, [_P, _L, _D, _D, _P, _P]),
     "fem_density_filter": (_I, [_P, _L, _P, _P, _L, _P, _P, _P, _I, _I, _D, _D, _P, _P, _P, _P, _P]),
     "fem_oc_update": (_I, [_P, _P, _P, _P, _L, _D, _D, _D, _I, _P, _P, _P, _P]),
+    "fem_xd_lumped_mass": (_I, [_P, _D, _P, _P]),
+    "fem_xd_stable_dt": (_I, [_P, _P, _L, _D, _D, _D, _P, _P, _P]),
+    "fem_xd_create": (_I, [_P, _I, _D, _P, _P, _D, _P, _P, _P, _P, ctypes.POINTER(_P)]),
+    "fem_xd_destroy": (_I, [_P]),
+    "fem_xd_start": (_I, [_P, _P, _P, _P, _D, _P]),
+    "fem_xd_run": (_I, [_P, _L, _D, ctypes.POINTER(_D), _P, _L, _P, _P, _P, _P, _L, _P, _P]),
+    "fem_xd_force": (_I, [_P, _P, _P, _P]),
+    "fem_xd_status": (_I, [_P, ctypes.POINTER(_L), _P]),
+    "fem_xd_info": (_I, [_P, ctypes.POINTER(_L)]),
 }
 
 _lib = None

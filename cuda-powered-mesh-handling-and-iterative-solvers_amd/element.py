@@ -1094,6 +1094,39 @@ def density_filter(coords, elements, rho, passes=1, adjoint=False, device="cuda:
 
 __all__ += ["compute_c3d4_unit_energy", "density_filter"]
 
+
+# ============================================================================ explicit dynamics (csrc/explicit.hip)
+def compute_c3d4_lumped_mass(coords, elements, rho, device="cuda:0", dtype=torch.float64):
+    """m [N]: the lumped (row-sum) mass of a c3d4 mesh of uniform density, m_i = sum over the elements at node i of
+    rho V_e / 4, summed in the fixed order of the element-chunk layout (fem_xd_lumped_mass)."""
+    _sys.check_explicit_mesh("compute_c3d4_lumped_mass", coords, elements, rho, 1.0, 0.0)
+    dev, coords, elements = _prep(coords, elements, device)
+    op = _sys.MatFreeOperator(coords, elements, "elastic", 1.0, 0.0)
+    try:
+        N = coords.shape[0]
+        m = torch.zeros(max(N, 1), dtype=F64, device=dev)
+        C.check(C.lib().fem_xd_lumped_mass(op.h, float(rho), C.ptr(m), C.stream(dev)), "fem_xd_lumped_mass")
+    finally:
+        op.close()
+    return _out(m[:N], device, dtype)
+
+
+def compute_c3d4_stable_time_step(coords, elements, E, nu, rho, device="cuda:0", dtype=torch.float64):
+    """(dt, dt_e [M]): the guaranteed stable step of explicit central differences with the lumped mass,
+    dt_e = 1 / (c_d sqrt(sum_a |g_a|^2)), c_d^2 = (max(lam, 0) + 2 mu) / rho, dt = min_e dt_e <= 2 / omega_max
+    (fem_xd_stable_dt; the bound's proof sketch is in DESIGN §8u). dt is inf for a mesh of no element."""
+    _sys.check_explicit_mesh("compute_c3d4_stable_time_step", coords, elements, rho, E, nu)
+    dev, coords, elements = _prep(coords, elements, device)
+    M = elements.shape[0]
+    dte = torch.empty(max(M, 1), dtype=F64, device=dev)
+    out = torch.empty(1, dtype=F64, device=dev)
+    C.check(C.lib().fem_xd_stable_dt(C.ptr(coords), C.ptr(elements), M, float(E), float(nu), float(rho), C.ptr(dte),
+                                     C.ptr(out), C.stream(dev)), "fem_xd_stable_dt")
+    return float(out.item()), _out(dte[:M], device, dtype)
+
+
+__all__ += ["compute_c3d4_lumped_mass", "compute_c3d4_stable_time_step"]
+
 __all__ += ["geometric_integration_points", "compute_geometric_stiffness"]
 
 __all__ += [

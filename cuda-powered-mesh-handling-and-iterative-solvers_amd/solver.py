@@ -964,6 +964,103 @@ def transient_solver(K, M, elements, F, fixed, num_nodes, dt, steps, amplitude=N
     return ret + (res,) if return_info else ret
 
 
+# ============================================================================ explicit dynamics
+# Impact, wave propagation and fast large-deformation loading: central differences with the lumped mass on the element
+# chunks (system.ExplicitDynamics, csrc/explicit.hip). No matrix, no linear solve; the step size comes from
+# the mesh. No counterpart in the reference.
+def _check_explicit(what, coords, elements, F, fixed, rho, E, nu, steps, dt, safety, material, amplitude, u0, v0,
+                    damping, record, energy_every):
+    """Every ValueError of explicit_dynamics_solver -- before any device call. Returns (fixed-dof mask [N,3] bool on
+    the host, record node ids or None)."""
+    N, _ = _sys.check_explicit_mesh(what, coords, elements, rho, E, nu)
+    if elements.numel() and (int(elements.min()) < 0 or _max_node(elements) > N):
+        raise ValueError(f"{what}: the mesh references a node outside [0, {N})")
+    if material not in C.EXPLICIT_MATERIALS:
+        raise ValueError(f"{what}: unknown material {material!r} (supported: "
+                         f"{', '.join(sorted(C.EXPLICIT_MATERIALS))})")
+    _sys.check_explicit_run(what, steps, dt)
+    steps = int(steps)
+    if dt is None and not 0.0 < float(safety) <= 1.0:
+        raise ValueError(f"{what}: safety must lie in (0, 1], got {safety}")
+    if not float(damping) >= 0.0:
+        raise ValueError(f"{what}: damping must be >= 0, got {damping}")
+    if int(energy_every) < 0:
+        raise ValueError(f"{what}: energy_every must be >= 0, got {energy_every}")
+    if not torch.is_tensor(F) or tuple(F.shape) != (N, 3):
+        raise ValueError(f"{what}: F must be [{N}, 3], got {tuple(getattr(F, 'shape', ()))}")
+    if amplitude is not None:
+        if torch.is_tensor(amplitude):
+            if amplitude.dim() != 1 or amplitude.numel() != steps + 1:
+                raise ValueError(f"{what}: amplitude must hold steps + 1 = {steps + 1} values (t_0 .. t_steps), "
+                                 f"got {tuple(amplitude.shape)}")
+        elif not callable(amplitude):
+            raise ValueError(f"{what}: amplitude must be None, a tensor [steps + 1] or a callable of t")
+    for name, x in (("u0", u0), ("v0", v0)):
+        if x is not None and (not torch.is_tensor(x) or tuple(x.shape) != (N, 3)):
+            raise ValueError(f"{what}: {name} must be [{N}, 3]")
+    mask = _fixed_mask(what, fixed, N)
+    rec = None
+    if record is not None:
+        rec = torch.as_tensor(record).to(LONG).reshape(-1)
+        if rec.numel() and (int(rec.min()) < 0 or int(rec.max()) >= N):
+            raise ValueError(f"{what}: a recorded node lies outside [0, {N})")
+    return mask, rec
+
+
+def explicit_dynamics_solver(coords, elements, F, fixed, rho, E, nu, steps, dt=None, safety=0.9, material="linear",
+                             amplitude=None, u0=None, v0=None, damping=0.0, record=None, energy_every=0,
+                             device="cuda:0", dtype=torch.float64, return_info=False):
+    """Response in time of a c3d4 mesh under M a + alpha M v + f_int(u) = amp(t) F by explicit central differences
+    (leapfrog) with the lumped mass, `steps` steps of `dt`. material: "linear" (small strain), "svk" or "neo_hookean"
+    (total Lagrangian, as nonlinear_static_solver); uniform rho, E, nu; damping = alpha (mass-proportional).
+    fixed: node ids, or a bool / uint8 [N,3] mask of single dofs (rollers). dt=None takes safety x the guaranteed
+    stable step of compute_c3d4_stable_time_step (a bound for the linear operator: a stiffening nonlinear response may
+    need less); a given dt is used as is. F, amplitude (None: suddenly applied; a tensor [steps + 1] of the values at
+    t_0 .. t_steps; a callable of t), u0, v0 and record (node ids -> [steps + 1, len(record), 3]) as transient_solver.
+    An element that inverts (det F <= 0: it then carries no force) or a non-finite value does not stop the run: one line
+    `Explicit solver: ...` is printed and the state reached is returned; system.ExplicitResult.status tells.
+    Returns (u, v, a) [N,3] at the last step in `dtype`; with return_info also the system.ExplicitResult (with `dt`)."""
+    what = "explicit_dynamics_solver"
+    mask, rec = _check_explicit(what, coords, elements, F, fixed, rho, E, nu, steps, dt, safety, material, amplitude,
+                                u0, v0, damping, record, energy_every)
+    steps = int(steps)
+    dev = _dev(device)
+    cd = coords.to(device=dev, dtype=F64).contiguous()
+    el = elements.to(device=dev, dtype=LONG).contiguous()
+    N = cd.shape[0]
+    xd = _sys.ExplicitDynamics(cd, el, rho, E, nu, material, mask.to(dev), damping)
+    try:
+        if dt is None:
+            dt = float(safety) * xd.stable_dt()[0]
+            if not dt < float("inf"):
+                dt = 1.0   # no element: nothing moves, any step will do
+        dt = float(dt)
+        if amplitude is None:
+            amps = [1.0] * (steps + 1)
+        elif torch.is_tensor(amplitude):
+            amps = [float(x) for x in amplitude.to(dtype=F64).cpu()]
+        else:
+            amps = [float(amplitude(k * dt)) for k in range(steps + 1)]
+        Fd = F.to(device=dev, dtype=F64).reshape(-1).contiguous()
+        xd.start(u0, v0, Fd, amps[0])
+        rdofs = None
+        if rec is not None:
+            rdofs = (rec.to(dev).unsqueeze(-1) * 3 + torch.arange(3, device=dev)).reshape(-1)
+        res = xd.run(steps, dt, Fd, amps, record=rdofs, energy_every=int(energy_every))
+        if res.status != _sys.XD_OK:
+            print(f"Explicit solver: status {res.status} at step {res.stop_step} (dt = {dt:.6e}); the state after "
+                  f"{steps} steps is returned")
+        if rec is not None:   # rows 0 .. steps - 1 from the run, row `steps` the state reached
+            last = (xd.u[rdofs], xd.v[rdofs], xd.a[rdofs])
+            res.rec_u, res.rec_v, res.rec_a = (torch.cat((r, x.view(1, -1))).reshape(steps + 1, -1, 3)
+                                               for r, x in zip((res.rec_u, res.rec_v, res.rec_a), last))
+        out = torch.device(device)
+        ret = tuple(x.view(N, 3).to(device=out, dtype=dtype).clone() for x in (xd.u, xd.v, xd.a))
+    finally:
+        xd.close()
+    return ret + (res,) if return_info else ret
+
+
 # ============================================================================ nonlinear statics
 # Large-displacement statics of c3d4 meshes: Newton's method on the total-Lagrangian residual with the hyperelastic
 # tangent of csrc/nonlinear.hip, the matrix refilled in place every iteration (system.NewtonStatics; DESIGN §8n).

@@ -2148,8 +2148,208 @@ class NewmarkIntegrator:
             pass
 
 
+# ============================================================================ explicit dynamics (csrc/explicit.hip)
+XD_OK, XD_INVERTED, XD_DIVERGED = "OK", "INVERTED", "DIVERGED"
+
+
+def check_explicit_mesh(what, coords, elements, rho, E, nu):
+    """The ValueErrors shared by everything explicit -- no device call: c3d4 mesh shapes, rho > 0, E > 0 and nu in
+    (-1, 0.5). Returns (N, M)."""
+    if not torch.is_tensor(coords) or coords.dim() != 2 or coords.shape[1] != 3:
+        raise ValueError(f"{what}: coords must be [N, 3], got {tuple(getattr(coords, 'shape', ()))}")
+    if not torch.is_tensor(elements) or elements.dim() != 2 or elements.shape[1] != 4:
+        raise ValueError(f"{what}: c3d4 connectivity [M, 4] expected, got {tuple(getattr(elements, 'shape', ()))}")
+    if not float(rho) > 0.0:
+        raise ValueError(f"{what}: rho must be > 0, got {rho}")
+    if not float(E) > 0.0:
+        raise ValueError(f"{what}: E must be > 0, got {E}")
+    if not -1.0 < float(nu) < 0.5:
+        raise ValueError(f"{what}: nu must lie in (-1, 0.5), got {nu}")
+    return coords.shape[0], elements.shape[0]
+
+
+def check_explicit_run(what, steps, dt):
+    if int(steps) != steps or int(steps) < 0:
+        raise ValueError(f"{what}: steps must be an integer >= 0, got {steps}")
+    if dt is not None and not float(dt) > 0.0:
+        raise ValueError(f"{what}: dt must be > 0, got {dt}")
+
+
+@dataclass
+class ExplicitResult:
+    """ExplicitDynamics.run: the run's steps n0 .. n0 + steps - 1 (counted from the start). The recorded rows hold the
+    state at the beginning of each step, t = n dt; the state at the end of the run is the integrator's u, v, a."""
+    steps_done: int                # steps taken by this run
+    status: str                    # XD_OK, XD_INVERTED (an element with det F <= 0) or XD_DIVERGED (a non-finite value)
+    stop_step: int                 # the first step (from the start) at which that happened, -1 for XD_OK
+    dt: float
+    first_step: int = 0            # n0
+    rec_u: torch.Tensor = None     # [steps, len(record)] (device)
+    rec_v: torch.Tensor = None
+    rec_a: torch.Tensor = None
+    t_energy: torch.Tensor = None  # [rows] (host): the times of the energy rows (steps n with n % energy_every == 0)
+    kinetic: torch.Tensor = None   # sum m v_n^2 / 2
+    strain: torch.Tensor = None    # sum V W (u_n)
+    ext_power: torch.Tensor = None  # amp_n F . v_n
+    ext_work: torch.Tensor = None   # amp_n F . u_n: the work of the load held at its current value (the potential of a
+                                    # constant load; kinetic + strain - ext_work is then conserved without damping)
+
+
+@_scoped
+class ExplicitDynamics:
+    """Explicit central-difference dynamics of a c3d4 mesh (include/fem355.h fem_xd_*, csrc/explicit.hip):
+    M a + alpha M v + f_int(u) = amp(t) F with the lumped mass m_i = sum rho V_e / 4, `damping` = alpha, integrated in
+    leapfrog form. A step is one chunk kernel (the internal force of `material` on the MatFreeOperator layout this
+    object owns: "linear", "svk" or "neo_hookean") and one vector kernel; nothing is assembled and nothing is solved.
+    fixed_mask: uint8 / bool [3N] or [N,3], the dofs held at u = v = a = 0. Uniform rho, E, nu. The step size is the
+    caller's: stable_dt() returns a guaranteed bound."""
+
+    def __init__(self, coords, elements, rho, E, nu, material="linear", fixed_mask=None, damping=0.0):
+        what = "ExplicitDynamics"
+        N, M = check_explicit_mesh(what, coords, elements, rho, E, nu)
+        if material not in C.EXPLICIT_MATERIALS:
+            raise ValueError(f"{what}: unknown material {material!r} (supported: "
+                             f"{', '.join(sorted(C.EXPLICIT_MATERIALS))})")
+        if not float(damping) >= 0.0:
+            raise ValueError(f"{what}: damping must be >= 0, got {damping}")
+        if fixed_mask is not None and (not torch.is_tensor(fixed_mask) or fixed_mask.numel() != 3 * N):
+            raise ValueError(f"{what}: fixed_mask must hold {3 * N} values")
+        self.lib = C.lib()
+        self.material, self.rho, self.E, self.nu, self.damping = material, float(rho), float(E), float(nu), float(damping)
+        self.op = MatFreeOperator(coords, elements, "elastic", E, nu)
+        self.device, self.N, self.M, self.n = self.op.device, N, M, 3 * N
+        dev = self.device
+        self.h = ctypes.c_void_p()
+        self.mass = torch.zeros(max(N, 1), dtype=F64, device=dev)[:N]
+        C.check(self.lib.fem_xd_lumped_mass(self.op.h, self.rho, C.ptr(self.mass), C.stream(dev)), "fem_xd_lumped_mass")
+        self.fixed_mask = None if fixed_mask is None else \
+            (fixed_mask.to(dev) != 0).to(torch.uint8).contiguous().view(-1)
+        z = lambda: torch.zeros(self.n, dtype=F64, device=dev)
+        self.u, self.v, self.a = z(), z(), z()
+        C.check(self.lib.fem_xd_create(self.op.h, C.EXPLICIT_MATERIALS[material], self.rho, C.ptr(self.mass),
+                                       C.ptr(self.fixed_mask), self.damping, C.ptr(self.u), C.ptr(self.v),
+                                       C.ptr(self.a), C.stream(dev), ctypes.byref(self.h)), "fem_xd_create")
+        self.started = False
+
+    def _vec(self, x, what, null=True):
+        if x is None:
+            return None if null else torch.zeros(self.n, dtype=F64, device=self.device)
+        x = x.to(device=self.device, dtype=F64).reshape(-1).contiguous()
+        if x.numel() != self.n:
+            raise ValueError(f"ExplicitDynamics: {what} must hold {self.n} values, got {x.numel()}")
+        return x
+
+    def stable_dt(self):
+        """(dt, per-element dt [M] on the device): dt = min_e 1 / (c_d sqrt(sum_a |g_a|^2)), c_d^2 = (max(lam, 0) + 2 mu) / rho,
+        which is <= 2 / omega_max of the lumped-mass pencil (inf for a mesh of no element)."""
+        dev = self.device
+        dte = torch.empty(max(self.M, 1), dtype=F64, device=dev)
+        out = torch.empty(1, dtype=F64, device=dev)
+        C.check(self.lib.fem_xd_stable_dt(C.ptr(self.op.coords), C.ptr(self.op.elements), self.M, self.E, self.nu,
+                                          self.rho, C.ptr(dte), C.ptr(out), C.stream(dev)), "fem_xd_stable_dt")
+        return float(out.item()), dte[: self.M]
+
+    def internal_force(self, u):
+        """f_int(u) [3N] of the material (one chunk kernel and the slot sums); the state is untouched."""
+        u = self._vec(u, "u", null=False)
+        f = torch.empty(self.n, dtype=F64, device=self.device)
+        C.check(self.lib.fem_xd_force(self.h, C.ptr(u), C.ptr(f), C.stream(self.device)), "fem_xd_force")
+        return f
+
+    def start(self, u0=None, v0=None, F=None, amp=1.0):
+        """Set the state at t = 0: u0, v0 (zero on the fixed dofs) and a_0 = (amp F - f_int(u0)) / m - alpha v0."""
+        u0, v0, F = self._vec(u0, "u0"), self._vec(v0, "v0"), self._vec(F, "F")
+        C.check(self.lib.fem_xd_start(self.h, C.ptr(u0), C.ptr(v0), C.ptr(F), float(amp), C.stream(self.device)),
+                "fem_xd_start")
+        self.started = True
+        return self
+
+    def status(self):
+        """(status, stop_step) since the start; synchronises."""
+        w = (ctypes.c_int64 * 2)()
+        C.check(self.lib.fem_xd_status(self.h, w, C.stream(self.device)), "fem_xd_status")
+        inv, nf = int(w[0]), int(w[1])
+        if nf >= 0 and (inv < 0 or nf < inv):
+            return XD_DIVERGED, nf
+        if inv >= 0:
+            return XD_INVERTED, inv
+        return XD_OK, -1
+
+    def steps_taken(self):
+        w = (ctypes.c_int64 * 4)()
+        C.check(self.lib.fem_xd_info(self.h, w), "fem_xd_info")
+        return int(w[0])
+
+    def run(self, steps, dt, F=None, amps=1.0, record=None, energy_every=0):
+        """`steps` steps of `dt` from the state reached, all enqueued at once (two launches per step). F [3N]: the load
+        pattern (None: no load); amps: a number, or the load factors at the run's times -- steps + 1 values (t_n0 ..
+        t_n0+steps; with `steps` values the last is held). record: dof indices whose u, v, a are kept per step;
+        energy_every = m > 0: the energies at the steps n with n % m == 0 counted from the start. Consecutive runs
+        with the same dt continue the same trajectory bit for bit. Returns an ExplicitResult (reads the status words
+        back: one synchronisation at the end)."""
+        what = "ExplicitDynamics.run"
+        check_explicit_run(what, steps, dt)
+        steps, dt, every = int(steps), float(dt), int(energy_every)
+        if every < 0:
+            raise ValueError(f"{what}: energy_every must be >= 0, got {energy_every}")
+        if not self.started:
+            self.start()
+        dev = self.device
+        F = self._vec(F, "F")
+        if isinstance(amps, (int, float)):
+            al = [float(amps)] * (steps + 1)
+        else:
+            al = [float(x) for x in (amps.cpu() if torch.is_tensor(amps) else amps)]
+            if len(al) == steps and steps > 0:
+                al.append(al[-1])
+            if len(al) != steps + 1:
+                raise ValueError(f"{what}: amps must hold steps + 1 = {steps + 1} values (or steps), got {len(al)}")
+        n0 = self.steps_taken()
+        res = ExplicitResult(steps, XD_OK, -1, dt, n0)
+        nrec, rdofs, inv, ru, rv, ra = 0, None, None, None, None, None
+        if record is not None:
+            rec = torch.as_tensor(record).to(device=dev, dtype=torch.int64).reshape(-1)
+            if rec.numel() and (int(rec.min()) < 0 or int(rec.max()) >= self.n):
+                raise ValueError(f"{what}: a recorded dof lies outside [0, {self.n})")
+            rdofs, inv = torch.unique(rec, return_inverse=True)   # the kernel takes distinct dofs
+            nrec = rdofs.numel()
+            ru, rv, ra = (torch.zeros((steps, max(nrec, 1)), dtype=F64, device=dev)[:, :nrec].contiguous()
+                          for _ in range(3))
+        rows = [n for n in range(n0, n0 + steps) if every and n % every == 0]
+        en = torch.zeros((max(len(rows), 1), 4), dtype=F64, device=dev) if every else None
+        amp_c = (ctypes.c_double * (steps + 1))(*al)
+        if self.n and steps:
+            C.check(self.lib.fem_xd_run(self.h, steps, dt, amp_c, C.ptr(F), nrec, C.ptr(rdofs) if nrec else None,
+                                        C.ptr(ru) if nrec else None, C.ptr(rv) if nrec else None,
+                                        C.ptr(ra) if nrec else None, every, C.ptr(en), C.stream(dev)), "fem_xd_run")
+        elif steps:
+            C.check(self.lib.fem_xd_run(self.h, steps, dt, amp_c, None, 0, None, None, None, None, 0, None,
+                                        C.stream(dev)), "fem_xd_run")
+        if record is not None:
+            res.rec_u, res.rec_v, res.rec_a = ru[:, inv], rv[:, inv], ra[:, inv]
+        if every:
+            e = en[: len(rows)].cpu()
+            res.t_energy = torch.tensor(rows, dtype=F64) * dt
+            res.kinetic, res.strain, res.ext_power, res.ext_work = e[:, 0], e[:, 1], e[:, 2], e[:, 3]
+        res.status, res.stop_step = self.status()
+        return res
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.fem_xd_destroy(self.h)
+            self.h = ctypes.c_void_p()
+        if getattr(self, "op", None) is not None:
+            self.op.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ============================================================================ nonlinear statics (csrc/nonlinear.hip)
-NL_OK, NL_MAX_ITER, NL_LINE_SEARCH_FAILED, NL_LINEAR_SOLVE_FAILED = "OK", "MAX_ITER", "LINE_SEARCH_FAILED", \
+NL_OK,NL_MAX_ITER, NL_LINE_SEARCH_FAILED, NL_LINEAR_SOLVE_FAILED = "OK", "MAX_ITER", "LINE_SEARCH_FAILED", \
     "LINEAR_SOLVE_FAILED"
 
 

@@ -1130,6 +1130,54 @@ int fem_oc_update(const double* rho, const double* dc, const double* V, const in
                   double volfrac, double move, double rho_min, int n_bisect, double* work, double* rho_new,
                   double* out, fem_stream_t stream);
 
+/* ---- explicit dynamics (csrc/explicit.hip): central differences on the element chunks of a fem_mf layout
+ * M a + alpha M v + f_int(u) = amp(t) f_ext with the lumped mass M, integrated in leapfrog form:
+ *   v_{n+1/2} = ((1 - alpha dt/2) v_{n-1/2} + dt (amp_n f_ext - f_int(u_n)) / m) / (1 + alpha dt/2),
+ *   u_{n+1} = u_n + dt v_{n+1/2};  the first step after a start (or a change of dt) takes v_{1/2} = v_0 + (dt/2) a_0.
+ * Materials: FEM_MAT_LINEAR (small strain, the operator of fem_mf_apply), FEM_MAT_SVK, FEM_MAT_NEO_HOOKEAN (total
+ * Lagrangian, the forces of fem_tet4_nl). Everything is stream-ordered; only fem_xd_status synchronises.
+ * fem_xd_lumped_mass: mass [N] = sum over the node's elements of rho V_e / 4 in the layout's fixed order (0 for a node
+ *   of no element). Uses the layout's own scratch: one stream at a time, as fem_mf_apply.
+ * fem_xd_stable_dt: dt_e [M] (nullable) = 1 / (c_d sqrt(sum_a |g_a|^2)), c_d^2 = (max(lam, 0) + 2 mu) / rho, and
+ *   *dt_min (device) = min_e dt_e (+inf for M == 0) <= 2 / omega_max of the lumped-mass pencil: with the lumped
+ *   element mass rho V / 4 the largest element eigenvalue is <= 4 c_d^2 sum_a |g_a|^2. A degenerate element gives 0.
+ * fem_xd_create: an integrator on the layout `mf` (FEM_KIND_ELASTIC; its E, nu are the material's; it must outlive
+ *   the integrator). mass [N] from fem_xd_lumped_mass, mask [3N] uint8 (nullable; != 0: the dof stays at u = v = a = 0;
+ *   a node of zero mass is held as well), alpha >= 0 the mass-proportional damping, u, v, a [3N] the caller's state
+ *   arrays: after fem_xd_start and after every fem_xd_run they hold u_n, v_n, a_n of the time reached.
+ * fem_xd_start: u <- u0, v <- v0 (NULL: zero), step 0, status cleared, a <- (amp0 fext - f_int(u0)) / m - alpha v0
+ *   (fext [3N] nullable).
+ * fem_xd_run: nsteps steps of dt from the state reached: two launches per step (force, update) and, on the steps n
+ *   with n % energy_every == 0 (n counted from the start), a one-workgroup sum; no host synchronisation. amps (host,
+ *   [nsteps + 1], read during the call): the load factor at the run's times t_n .. t_{n + nsteps} (unused with fext
+ *   NULL). rec_dofs [nrec] (device, distinct dofs): row k of rec_u / rec_v / rec_a [nsteps, nrec] gets u, v =
+ *   (v_{-1/2} + v_{+1/2}) / 2 and a of those dofs at the run's step k (before its advance). energies [rows, 4]
+ *   (device): per energy step (kinetic sum m v_n^2 / 2, strain, external power amp f_ext . v_n, amp f_ext . u_n).
+ *   Consecutive runs with the same dt continue the same trajectory bit for bit.
+ *   An element with det F <= 0 (nonlinear materials) or a degenerate reference element contributes zero force and
+ *   records the first such step; the first step that produced a non-finite u or v is recorded too. Neither stops the
+ *   run.
+ * fem_xd_force: fint [3N] = f_int(u) for any u (the integrator's state is untouched except that an inverted element
+ *   is recorded at the current step).
+ * fem_xd_status: out2 = (first inverted step, first non-finite step), -1 for none; synchronises the stream.
+ * fem_xd_info: out4 = (steps taken since the start, chunks, workgroups of the update, values per energy row). */
+enum { FEM_MAT_LINEAR = 2 };
+typedef struct fem_xd fem_xd;
+int fem_xd_lumped_mass(fem_mf* mf, double rho, double* mass, fem_stream_t stream);
+int fem_xd_stable_dt(const double* coords, const int64_t* conn, int64_t M, double E, double nu, double rho,
+                     double* dt_e, double* dt_min, fem_stream_t stream);
+int fem_xd_create(fem_mf* mf, int material, double rho, const double* mass, const uint8_t* mask, double alpha,
+                  double* u, double* v, double* a, fem_stream_t stream, fem_xd** out);
+int fem_xd_destroy(fem_xd* h);
+int fem_xd_start(fem_xd* h, const double* u0, const double* v0, const double* fext, double amp0,
+                 fem_stream_t stream);
+int fem_xd_run(fem_xd* h, int64_t nsteps, double dt, const double* amps, const double* fext, int64_t nrec,
+               const int64_t* rec_dofs, double* rec_u, double* rec_v, double* rec_a, int64_t energy_every,
+               double* energies, fem_stream_t stream);
+int fem_xd_force(fem_xd* h, const double* u, double* fint, fem_stream_t stream);
+int fem_xd_status(fem_xd* h, int64_t* out2, fem_stream_t stream);
+int fem_xd_info(fem_xd* h, int64_t* out4);
+
 #ifdef __cplusplus
 }
 #endif
