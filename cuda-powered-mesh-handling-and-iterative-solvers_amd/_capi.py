@@ -37,6 +37,8 @@ MAT_SVK, MAT_NEO_HOOKEAN = 0, 1   # include/fem355.h FEM_MAT_*
 MATERIALS = {"svk": MAT_SVK, "neo_hookean": MAT_NEO_HOOKEAN}
 MAT_LINEAR = 2
 EXPLICIT_MATERIALS = {"linear": MAT_LINEAR, **MATERIALS}   # explicit dynamics (fem_xd_*) also steps the linear operator
+SURFACE_KINDS = {"plane": 0, "sphere": 1, "cylinder": 2}   # include/fem355.h FEM_SURF_*
+XD_MAX_SURFACES = 8                                         # FEM_XD_MAX_SURFACES
 SHELL_LOCAL, SHELL_POINTS, SHELL_GLOBAL = 0, 1, 2   # include/fem355.h FEM_SHELL_*
 LOAD_NONE, LOAD_UNIFORM, LOAD_NODAL, LOAD_ELEMENT = 0, 1, 2, 3   # include/fem355.h FEM_LOAD_*
 MODAL_OUT_GM, MODAL_OUT_NORMS, MODAL_OUT_LEN = 576, 1152, 1168   # include/fem355.h FEM_MODAL_OUT_*
@@ -247,6 +249,9 @@ SIGNATURES = {
     "fem_xd_force": (_I, [_P, _P, _P, _P]),
     "fem_xd_status": (_I, [_P, ctypes.POINTER(_L), _P]),
     "fem_xd_info": (_I, [_P, ctypes.POINTER(_L)]),
+    "fem_xd_contact": (_I, [_P, _L, ctypes.POINTER(_D), _D, _D, _P, _P]),
+    "fem_xd_run_contact": (_I, [_P, _L, _D, ctypes.POINTER(_D), _P, _L, _P, _P, _P, _P, _L, _P, ctypes.POINTER(_D),
+                                ctypes.POINTER(_D), _L, _P, _P, _P]),
 }
 
 _lib = None

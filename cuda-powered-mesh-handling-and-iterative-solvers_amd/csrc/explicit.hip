@@ -17,6 +17,10 @@
 //                  (u_n, v_n = (v_{n-1/2} + v_{n+1/2}) / 2, a_n = (amp_n f_ext - f_int) / m - alpha v_n), the partials
 //                  of the kinetic energy, the external power and the external work term, and the non-finite word.
 //                  The same kernel without the advance gives v_n and a_n at the end of a run.
+//   k_xd_update_c: k_xd_update per node with the penalty contact force of up to 8 rigid surfaces (planes, spheres,
+//                  cylinders; normal force kappa m / dt^2 p, capped Coulomb friction in surface order), used in its
+//                  place when a contact set is attached; on history steps the per-surface partials, summed by
+//                  k_xd_csum (one workgroup, workgroup order).
 //   k_xd_sum     : one workgroup: the partials summed in workgroup order.
 //   k_xd_mass    : lumped mass, per chunk the rho V_e / 4 of every (element, corner) summed per local node in the
 //                  layout's order; the nodes' slots are then summed by k_mf_gather<1>.
@@ -393,6 +397,283 @@ __global__ void __launch_bounds__(XD_BLOCK) k_xd_update(MfOp op, XdUpd p, const 
     }
 }
 
+// ---------------------------------------------------------------- penalty contact with rigid surfaces
+constexpr int XD_MAXS = 8;    // surfaces of a contact set
+constexpr int XD_SV = 13;     // host values per surface: kind, inside, point, vector, radius, mu, velocity at a start
+constexpr int XD_NH = 5;      // values per surface of a history row: reaction (3), nodes in contact, largest penetration
+constexpr int XD_NCE = 3;     // values of a contact energy row: penalty energy, friction power, surface power
+constexpr int XD_CP = XD_MAXS * XD_NH + XD_NCE;   // partials per workgroup of the contact update
+
+struct XdSurf {
+    double c[3], n[3], w[3];   // reference point at this step, unit normal or axis, velocity of this step
+    double R, mu;
+    int kind, inside;
+};
+
+// the contact set as one launch sees it (by value in the kernel arguments)
+struct XdCon {
+    int ns;
+    double kappa;
+    double dt;                 // the step of the penalty stiffness kappa m / dt^2 and of the friction cap
+    const uint8_t* word;       // [N] or null: bit s set -> the node may touch surface s
+    double* cpart;             // [grid, XD_CP]
+    XdSurf s[XD_MAXS];
+};
+
+// penetration p = -g and the normal nu of surface S at x; false where S exerts nothing on the node: not penetrated
+// (g = 0 included), a NaN, or |r| = 0 (a node at a sphere's centre or on a cylinder's axis has no normal)
+__device__ __forceinline__ bool xd_gap(const XdSurf& S, const double x[3], double& pen, double nu[3]) {
+#pragma clang fp contract(off)
+    double r[3] = {x[0] - S.c[0], x[1] - S.c[1], x[2] - S.c[2]};
+    const double dn = (r[0] * S.n[0] + r[1] * S.n[1]) + r[2] * S.n[2];
+    double g;
+    if (S.kind == FEM_SURF_PLANE) {
+        g = dn;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) nu[q] = S.n[q];
+    } else {
+        if (S.kind == FEM_SURF_CYLINDER) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) r[q] = r[q] - dn * S.n[q];
+        }
+        const double rr = sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+        if (!(rr > 0.0)) return false;
+        const double sg = S.inside ? -1.0 : 1.0;
+        g = sg * (rr - S.R);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) nu[q] = sg * (r[q] / rr);
+    }
+    pen = -g;
+    return pen > 0.0;
+}
+
+__device__ __forceinline__ double xd_block_max256(double v, double* lds4) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmax(fmax(lds4[0], lds4[1]), fmax(lds4[2], lds4[3]));
+}
+
+// k_xd_update with a contact set: one thread per node (the gap, the normal and the friction cap need the node's three
+// components together). Per dof the arithmetic of k_xd_update in its order, with rm = (amp f_ext - f_int + f_c) / m
+// where the node touches a surface and (amp f_ext - f_int) / m where it does not: a run whose surfaces are never
+// touched gives the bits of k_xd_update. f_c = sum over the touched surfaces in index order of
+//   f_n = k p nu, k = kappa m / dt^2, and f_t = -min(mu |f_n|, m |vt| / sigma) vt / |vt|,
+// vt the tangential part of v* - w, v* the new half-step velocity formed with all normal forces and the friction of the
+// surfaces before this one (sigma = dt c2, dt / 2 for FROMV: what a unit force per unit mass adds to it); the
+// components on held dofs are dropped, and v* is 0 there. HIST: the per-surface partials of a history row (the surface
+// loop is then unrolled so that the sums stay in registers); ENERGY: also the three contact energy partials.
+template <bool FROMV, bool ADV, bool ENERGY, bool HIST>
+__global__ void __launch_bounds__(XD_BLOCK) k_xd_update_c(MfOp op, XdUpd p, XdCon ct, const double* __restrict__ slots) {
+#pragma clang fp contract(off)
+    __shared__ double red[4];
+    double ke = 0.0, pw = 0.0, wk = 0.0, ce = 0.0, fpw = 0.0, spw = 0.0;
+    double hr[HIST ? XD_MAXS : 1][XD_NH];
+#pragma unroll
+    for (int s = 0; s < (HIST ? XD_MAXS : 1); ++s)
+#pragma unroll
+        for (int j = 0; j < XD_NH; ++j) hr[s][j] = 0.0;
+    const int64_t N = p.n3 / 3;
+    const double sigma = FROMV ? 0.5 * ct.dt : ct.dt * p.c2;
+    constexpr int UNR = HIST ? XD_MAXS : 1;   // the surface loop of the friction pass: unrolled for the history sums
+    for (int64_t i = (int64_t)blockIdx.x * XD_BLOCK + threadIdx.x; i < N; i += (int64_t)gridDim.x * XD_BLOCK) {
+        const double m = p.mass[i];
+        const bool live = m > 0.0;   // a node of no element has no mass: it stays put and feels no surface
+        bool fixed[3];
+        double un[3], vo[3], num[3], fx[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const int64_t d = 3 * i + q;
+            fixed[q] = (p.mask && p.mask[d]) || !live;
+            un[q] = vo[q] = num[q] = fx[q] = 0.0;
+            if (!fixed[q]) {
+                double fint = 0.0;
+                const int k0 = op.nptr[i], k1 = op.nptr[i + 1];
+                for (int k = k0; k < k1; ++k) fint += slots[(int64_t)(op.spos ? k : op.nslot[k]) * 3 + q];
+                fx[q] = p.fext ? p.amp * p.fext[d] : 0.0;
+                num[q] = fx[q] - fint;
+                un[q] = p.u[d];
+                vo[q] = FROMV ? p.v[d] : p.vh[d];
+            }
+        }
+        double fc[3] = {0.0, 0.0, 0.0}, ft[3] = {0.0, 0.0, 0.0};   // contact force, its friction part
+        double ftw = 0.0;                                           // sum f_t . w
+        unsigned hit = 0;
+        const unsigned word = live ? (ct.word ? ct.word[i] : 0xffu) : 0u;
+        if (word) {
+            const double x[3] = {op.X[3 * i] + un[0], op.X[3 * i + 1] + un[1], op.X[3 * i + 2] + un[2]};
+            const double kp = ct.kappa * m / (ct.dt * ct.dt);
+            double fn[3] = {0.0, 0.0, 0.0};
+            for (int s = 0; s < ct.ns; ++s) {
+                if (!((word >> s) & 1u)) continue;
+                double pen, nu[3];
+                if (!xd_gap(ct.s[s], x, pen, nu)) continue;
+                hit |= 1u << s;
+#pragma unroll
+                for (int q = 0; q < 3; ++q) fn[q] += (kp * pen) * nu[q];
+            }
+            if (hit) {
+                double vs[3];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const double rn = (num[q] + fn[q]) / m;
+                    const double t = FROMV ? vo[q] + 0.5 * ct.dt * (rn - p.alpha * vo[q])
+                                           : (p.c1 * vo[q] + ct.dt * rn) * p.c2;
+                    vs[q] = fixed[q] ? 0.0 : t;
+                }
+#pragma unroll UNR
+                for (int s = 0; s < XD_MAXS; ++s) {
+                    if (s >= ct.ns || !((hit >> s) & 1u)) continue;
+                    const XdSurf& S = ct.s[s];
+                    double pen, nu[3];
+                    (void)xd_gap(S, x, pen, nu);
+                    const double fnm = kp * pen;
+                    double fs[3], rel[3];
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) {
+                        fs[q] = fixed[q] ? 0.0 : fnm * nu[q];
+                        rel[q] = vs[q] - S.w[q];
+                    }
+                    const double vnn = (rel[0] * nu[0] + rel[1] * nu[1]) + rel[2] * nu[2];
+                    double vt[3];
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) vt[q] = rel[q] - vnn * nu[q];
+                    const double vtm = sqrt((vt[0] * vt[0] + vt[1] * vt[1]) + vt[2] * vt[2]);
+                    if (S.mu > 0.0 && vtm > 0.0) {
+                        const double cap = fmin(S.mu * fnm, m * vtm / sigma);
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) {
+                            const double f = fixed[q] ? 0.0 : -(cap * (vt[q] / vtm));
+                            vs[q] += sigma * f / m;
+                            fs[q] += f;
+                            ft[q] += f;
+                            ftw += f * S.w[q];
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) fc[q] += fs[q];
+                    if (ADV && HIST) {
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) hr[HIST ? s : 0][q] -= fs[q];
+                        hr[HIST ? s : 0][3] += 1.0;
+                        hr[HIST ? s : 0][4] = fmax(hr[HIST ? s : 0][4], pen);
+                    }
+                    if (ADV && ENERGY) {
+                        ce += 0.5 * kp * pen * pen;
+                        spw += (fs[0] * S.w[0] + fs[1] * S.w[1]) + fs[2] * S.w[2];
+                    }
+                }
+            }
+        }
+        double vnv[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const int64_t d = 3 * i + q;
+            double vn = 0.0, an = 0.0, vhn = 0.0;
+            if (!fixed[q]) {
+                const double rm = (hit ? num[q] + fc[q] : num[q]) / m;
+                if (FROMV) {
+                    vn = vo[q];
+                    an = rm - p.alpha * vn;
+                    vhn = vn + 0.5 * p.dt * an;
+                } else {
+                    vhn = (p.c1 * vo[q] + p.dt * rm) * p.c2;
+                    vn = 0.5 * (vo[q] + vhn);
+                    an = rm - p.alpha * vn;
+                }
+            }
+            vnv[q] = vn;
+            if (ADV) {
+                const double unew = fixed[q] ? 0.0 : un[q] + p.dt * vhn;
+                p.u[d] = unew;
+                p.vh[d] = vhn;
+                if (!(fabs(unew) <= 1.79769313486231570815e308) || !(fabs(vhn) <= 1.79769313486231570815e308))
+                    atomicMin(p.status + 1, p.step);
+                if (p.recmap) {
+                    const int col = p.recmap[d];
+                    if (col >= 0) {
+                        p.ru[col] = un[q];
+                        p.rv[col] = vn;
+                        p.ra[col] = an;
+                    }
+                }
+                if (ENERGY) {
+                    ke += 0.5 * m * vn * vn;
+                    pw += fx[q] * vn;
+                    wk += fx[q] * un[q];
+                }
+            } else {
+                p.v[d] = vn;
+                p.a[d] = an;
+                if (FROMV) {
+                    p.u[d] = un[q];
+                    p.vh[d] = 0.0;
+                }
+            }
+        }
+        if (ADV && ENERGY && hit) fpw += ((ft[0] * vnv[0] + ft[1] * vnv[1]) + ft[2] * vnv[2]) - ftw;
+    }
+    if (ADV && ENERGY) {
+        ke = block_sum256(ke, red);
+        pw = block_sum256(pw, red);
+        wk = block_sum256(wk, red);
+        ce = block_sum256(ce, red);
+        fpw = block_sum256(fpw, red);
+        spw = block_sum256(spw, red);
+        if (threadIdx.x == 0) {
+            p.kpart[(int64_t)blockIdx.x * 3] = ke;
+            p.kpart[(int64_t)blockIdx.x * 3 + 1] = pw;
+            p.kpart[(int64_t)blockIdx.x * 3 + 2] = wk;
+            double* c = ct.cpart + (int64_t)blockIdx.x * XD_CP + XD_MAXS * XD_NH;
+            c[0] = ce;
+            c[1] = fpw;
+            c[2] = spw;
+        }
+    }
+    if (ADV && HIST) {
+#pragma unroll
+        for (int s = 0; s < XD_MAXS; ++s) {
+            if (s >= ct.ns) break;
+#pragma unroll
+            for (int j = 0; j < XD_NH; ++j) {
+                const double t = j == 4 ? xd_block_max256(hr[HIST ? s : 0][j], red)
+                                        : block_sum256(hr[HIST ? s : 0][j], red);
+                if (threadIdx.x == 0) ct.cpart[(int64_t)blockIdx.x * XD_CP + s * XD_NH + j] = t;
+            }
+        }
+    }
+}
+
+// one workgroup: the contact partials of `nk` workgroups summed in workgroup order (the largest penetration: the
+// maximum), wave w the values w, w + 4, ...; hist [ns, XD_NH] and en [XD_NCE] are each written where given
+__global__ void __launch_bounds__(256) k_xd_csum(const double* __restrict__ cpart, int nk, int ns,
+                                                 double* __restrict__ hist, double* __restrict__ en) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int j = wave; j < XD_CP; j += 4) {
+        const bool energy = j >= XD_MAXS * XD_NH;
+        const int s = j / XD_NH, c = j - s * XD_NH;
+        if (energy ? en == nullptr : (hist == nullptr || s >= ns)) continue;   // the same in every lane
+        const bool mx = !energy && c == 4;
+        double v = 0.0;
+        for (int i = lane; i < nk; i += 64) {
+            const double t = cpart[(int64_t)i * XD_CP + j];
+            v = mx ? fmax(v, t) : v + t;
+        }
+        if (mx) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+        } else {
+            v = wave_sum(v);
+        }
+        if (lane == 0) {
+            if (energy) en[j - XD_MAXS * XD_NH] = v;
+            else hist[s * XD_NH + c] = v;
+        }
+    }
+}
+
 // one workgroup, a wave per value: lane l adds partials l, l + 64, ... in order, then the wave tree.
 // out = (kinetic, strain, external power, external work term)
 __global__ void __launch_bounds__(256) k_xd_sum(const double* __restrict__ kpart, int nk,
@@ -516,11 +797,17 @@ struct fem_xd {
     int64_t step = 0;
     bool started = false, fresh = true;
     double last_dt = 0.0;
+    // the contact set (fem_xd_contact): con.ns == 0 -> none; the surfaces hold their reference points and the
+    // velocities a start uses, dt0 the step of a start's penalty stiffness
+    XdCon con{};
+    double dt0 = 0.0;
+    int cgrid = 1;              // workgroups of the contact update (one thread per node)
+    double* cpart = nullptr;    // [cgrid, XD_CP], allocated with the first contact set
 };
 
 static void xd_free(fem_xd* h) {
     if (!h) return;
-    void* ps[] = {h->vh, h->slots, h->epart, h->kpart, h->recmap, h->status};
+    void* ps[] = {h->vh, h->slots, h->epart, h->kpart, h->recmap, h->status, h->cpart};
     for (void* p : ps)
         if (p) (void)hipFree(p);
     delete h;
@@ -559,6 +846,31 @@ static XdUpd xd_upd(const fem_xd* h, double dt, double amp, const double* fext, 
     p.kpart = h->kpart;
     p.status = h->status;
     return p;
+}
+
+// the contact set of one launch: the surfaces moved by off [ns, 3] (null: where they were attached) with the
+// velocities vel [ns, 3] (null: those of the attach call)
+static XdCon xd_con(const fem_xd* h, double dt, const double* off, const double* vel) {
+    XdCon c = h->con;
+    c.dt = dt;
+    c.cpart = h->cpart;
+    for (int s = 0; s < c.ns; ++s)
+        for (int q = 0; q < 3; ++q) {
+            if (off) c.s[s].c[q] = h->con.s[s].c[q] + off[3 * s + q];
+            if (vel) c.s[s].w[q] = vel[3 * s + q];
+        }
+    return c;
+}
+
+template <bool FROMV>
+static void xd_step_c_launch(const fem_xd* h, bool en, bool hist, const MfOp& op, const XdUpd& p, const XdCon& c,
+                             hipStream_t st) {
+    const dim3 g(h->cgrid), b(XD_BLOCK);
+    const double* sl = h->slots;
+    if (en && hist) hipLaunchKernelGGL((k_xd_update_c<FROMV, true, true, true>), g, b, 0, st, op, p, c, sl);
+    else if (en) hipLaunchKernelGGL((k_xd_update_c<FROMV, true, true, false>), g, b, 0, st, op, p, c, sl);
+    else if (hist) hipLaunchKernelGGL((k_xd_update_c<FROMV, true, false, true>), g, b, 0, st, op, p, c, sl);
+    else hipLaunchKernelGGL((k_xd_update_c<FROMV, true, false, false>), g, b, 0, st, op, p, c, sl);
 }
 
 extern "C" {
@@ -693,15 +1005,24 @@ int fem_xd_start(fem_xd* h, const double* u0, const double* v0, const double* fe
     xd_force_launch<false>(h, op, h->u, h->slots, 0ull, st);
     FEM_LAUNCHED();
     const XdUpd p = xd_upd(h, 0.0, amp0, fext, 0ull);
-    hipLaunchKernelGGL((k_xd_update<true, false, false>), dim3(h->ugrid), dim3(XD_BLOCK), 0, st, op, p,
-                       (const double*)h->slots);
+    if (h->con.ns > 0)
+        hipLaunchKernelGGL((k_xd_update_c<true, false, false, false>), dim3(h->cgrid), dim3(XD_BLOCK), 0, st, op, p,
+                           xd_con(h, h->dt0, nullptr, nullptr), (const double*)h->slots);
+    else
+        hipLaunchKernelGGL((k_xd_update<true, false, false>), dim3(h->ugrid), dim3(XD_BLOCK), 0, st, op, p,
+                           (const double*)h->slots);
     FEM_LAUNCHED();
     return FEM_OK;
 }
 
-int fem_xd_run(fem_xd* h, int64_t nsteps, double dt, const double* amps, const double* fext, int64_t nrec,
-               const int64_t* rec_dofs, double* rec_u, double* rec_v, double* rec_a, int64_t energy_every,
-               double* energies, fem_stream_t stream) {
+}  // extern "C"
+
+// fem_xd_run and fem_xd_run_contact (coff != null: the contact set's offsets and velocities per step)
+static int xd_run(fem_xd* h, int64_t nsteps, double dt, const double* amps, const double* fext, int64_t nrec,
+                  const int64_t* rec_dofs, double* rec_u, double* rec_v, double* rec_a, int64_t energy_every,
+                  double* energies, const double* coff, const double* cvel, int64_t contact_every, double* chist,
+                  double* cenergies, fem_stream_t stream) {
+    const bool ct = coff != nullptr;
     if (!h || !h->started || nsteps < 0 || !(dt > 0.0) || nrec < 0 || energy_every < 0 ||
         (nsteps > 0 && fext && !amps) || (nrec > 0 && (!rec_dofs || !rec_u || !rec_v || !rec_a)) ||
         (energy_every > 0 && !energies)) {
@@ -723,7 +1044,8 @@ int fem_xd_run(fem_xd* h, int64_t nsteps, double dt, const double* amps, const d
         FEM_LAUNCHED();
     }
     bool fromv = h->fresh || dt != h->last_dt;
-    int64_t erow = 0;
+    int64_t erow = 0, crow = 0;
+    const int ns = h->con.ns;
     const dim3 ug(h->ugrid), ub(XD_BLOCK);
     const double* sl = h->slots;
     for (int64_t k = 0; k < nsteps; ++k) {
@@ -737,6 +1059,22 @@ int fem_xd_run(fem_xd* h, int64_t nsteps, double dt, const double* amps, const d
             p.ru = rec_u + k * nrec;
             p.rv = rec_v + k * nrec;
             p.ra = rec_a + k * nrec;
+        }
+        if (ct) {
+            const bool hist = contact_every > 0 && (h->step + k) % contact_every == 0;
+            const XdCon c = xd_con(h, dt, coff + 3 * ns * k, cvel + 3 * ns * k);
+            if (fromv) xd_step_c_launch<true>(h, en, hist, op, p, c, st);
+            else xd_step_c_launch<false>(h, en, hist, op, p, c, st);
+            if (en) hipLaunchKernelGGL(k_xd_sum, dim3(1), dim3(256), 0, st, (const double*)h->kpart, h->cgrid,
+                                       (const double*)h->epart, h->nchunks, energies + XD_NE * erow);
+            if (en || hist)
+                hipLaunchKernelGGL(k_xd_csum, dim3(1), dim3(256), 0, st, (const double*)h->cpart, h->cgrid, ns,
+                                   hist ? chist + XD_NH * ns * crow : nullptr,
+                                   en ? cenergies + XD_NCE * erow : nullptr);
+            if (en) ++erow;
+            if (hist) ++crow;
+            fromv = false;
+            continue;
         }
         if (fromv) {
             if (en) hipLaunchKernelGGL((k_xd_update<true, true, true>), ug, ub, 0, st, op, p, sl);
@@ -759,8 +1097,89 @@ int fem_xd_run(fem_xd* h, int64_t nsteps, double dt, const double* amps, const d
     // v_n and a_n of the state reached (u and the half-step velocity stay as they are)
     xd_force_launch<false>(h, op, h->u, h->slots, (unsigned long long)h->step, st);
     const XdUpd p = xd_upd(h, dt, fext ? amps[nsteps] : 0.0, fext, (unsigned long long)h->step);
-    hipLaunchKernelGGL((k_xd_update<false, false, false>), ug, ub, 0, st, op, p, sl);
+    if (ct)
+        hipLaunchKernelGGL((k_xd_update_c<false, false, false, false>), dim3(h->cgrid), ub, 0, st, op, p,
+                           xd_con(h, dt, coff + 3 * ns * nsteps, cvel + 3 * ns * nsteps), sl);
+    else
+        hipLaunchKernelGGL((k_xd_update<false, false, false>), ug, ub, 0, st, op, p, sl);
     FEM_LAUNCHED();
+    return FEM_OK;
+}
+
+extern "C" {
+
+int fem_xd_run(fem_xd* h, int64_t nsteps, double dt, const double* amps, const double* fext, int64_t nrec,
+               const int64_t* rec_dofs, double* rec_u, double* rec_v, double* rec_a, int64_t energy_every,
+               double* energies, fem_stream_t stream) {
+    if (h && h->con.ns > 0 && h->N > 0) {
+        set_error("fem_xd_run: a contact set is attached; fem_xd_run_contact takes its surface motion");
+        return FEM_EARG;
+    }
+    return xd_run(h, nsteps, dt, amps, fext, nrec, rec_dofs, rec_u, rec_v, rec_a, energy_every, energies, nullptr,
+                  nullptr, 0, nullptr, nullptr, stream);
+}
+
+int fem_xd_run_contact(fem_xd* h, int64_t nsteps, double dt, const double* amps, const double* fext, int64_t nrec,
+                       const int64_t* rec_dofs, double* rec_u, double* rec_v, double* rec_a, int64_t energy_every,
+                       double* energies, const double* offsets, const double* velocities, int64_t contact_every,
+                       double* history, double* contact_energies, fem_stream_t stream) {
+    if (!h || h->con.ns <= 0 || !offsets || !velocities || contact_every < 0 || (contact_every > 0 && !history) ||
+        (energy_every > 0 && !contact_energies)) {
+        set_error("fem_xd_run_contact: needs an integrator with a contact set (fem_xd_contact), the offsets and "
+                  "velocities [nsteps + 1, surfaces, 3], the history rows with contact_every > 0 and the contact "
+                  "energy rows with energy_every > 0");
+        return FEM_EARG;
+    }
+    return xd_run(h, nsteps, dt, amps, fext, nrec, rec_dofs, rec_u, rec_v, rec_a, energy_every, energies, offsets,
+                  velocities, contact_every, history, contact_energies, stream);
+}
+
+int fem_xd_contact(fem_xd* h, int64_t nsurf, const double* surfaces, double kappa, double dt0,
+                   const uint8_t* node_word, fem_stream_t stream) {
+    (void)stream;
+    if (!h || nsurf < 0 || nsurf > XD_MAXS) {
+        set_error("fem_xd_contact: needs an integrator and 0 .. %d surfaces", XD_MAXS);
+        return FEM_EARG;
+    }
+    if (nsurf == 0) {
+        h->con = XdCon{};
+        return FEM_OK;
+    }
+    if (!surfaces || !(kappa > 0.0 && kappa < 4.0) || !(dt0 > 0.0)) {
+        set_error("fem_xd_contact: needs the surface table [nsurf, %d], 0 < kappa < 4 and dt0 > 0", XD_SV);
+        return FEM_EARG;
+    }
+    XdCon c{};
+    c.ns = (int)nsurf;
+    c.kappa = kappa;
+    c.word = node_word;
+    for (int s = 0; s < c.ns; ++s) {
+        const double* r = surfaces + XD_SV * s;
+        XdSurf& S = c.s[s];
+        S.kind = (int)r[0];
+        S.inside = r[1] != 0.0;
+        double nn = 0.0;
+        for (int q = 0; q < 3; ++q) {
+            S.c[q] = r[2 + q];
+            S.n[q] = r[5 + q];
+            S.w[q] = r[10 + q];
+            nn += S.n[q] * S.n[q];
+        }
+        S.R = r[8];
+        S.mu = r[9];
+        const bool round = S.kind == FEM_SURF_SPHERE || S.kind == FEM_SURF_CYLINDER;
+        if ((S.kind != FEM_SURF_PLANE && !round) || (double)S.kind != r[0] || !(S.mu >= 0.0) ||
+            (round && !(S.R > 0.0)) || (S.kind != FEM_SURF_SPHERE && !(fabs(nn - 1.0) <= 1e-12))) {
+            set_error("fem_xd_contact: surface %d needs a known kind, a unit normal or axis, a radius > 0 and mu >= 0", s);
+            return FEM_EARG;
+        }
+    }
+    if (!h->cpart) {
+        h->cgrid = stream_grid(h->N, XD_BLOCK);
+        FEM_HIP(hipMalloc(&h->cpart, sizeof(double) * XD_CP * (size_t)h->cgrid));
+    }
+    h->con = c;
+    h->dt0 = dt0;
     return FEM_OK;
 }
 

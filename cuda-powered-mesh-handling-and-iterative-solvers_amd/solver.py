@@ -1009,7 +1009,8 @@ def _check_explicit(what, coords, elements, F, fixed, rho, E, nu, steps, dt, saf
 
 def explicit_dynamics_solver(coords, elements, F, fixed, rho, E, nu, steps, dt=None, safety=0.9, material="linear",
                              amplitude=None, u0=None, v0=None, damping=0.0, record=None, energy_every=0,
-                             device="cuda:0", dtype=torch.float64, return_info=False):
+                             device="cuda:0", dtype=torch.float64, return_info=False, contact=None, penalty=0.5,
+                             contact_every=0):
     """Response in time of a c3d4 mesh under M a + alpha M v + f_int(u) = amp(t) F by explicit central differences
     (leapfrog) with the lumped mass, `steps` steps of `dt`. material: "linear" (small strain), "svk" or "neo_hookean"
     (total Lagrangian, as nonlinear_static_solver); uniform rho, E, nu; damping = alpha (mass-proportional).
@@ -1019,11 +1020,19 @@ def explicit_dynamics_solver(coords, elements, F, fixed, rho, E, nu, steps, dt=N
     t_0 .. t_steps; a callable of t), u0, v0 and record (node ids -> [steps + 1, len(record), 3]) as transient_solver.
     An element that inverts (det F <= 0: it then carries no force) or a non-finite value does not stop the run: one line
     `Explicit solver: ...` is printed and the state reached is returned; system.ExplicitResult.status tells.
+    contact: a list of up to 8 system.RigidSurface (planes, spheres, cylinders, solid or cavity, fixed or translating)
+    the nodes may not penetrate: frictional penalty contact with the normal stiffness penalty x m_i / dt^2 (DESIGN
+    §8v). With dt=None penalty may not exceed 4 (1 - safety^2), which keeps the step stable. contact_every = m > 0
+    keeps each surface's reaction, contact count and largest penetration every m-th step in the ExplicitResult.
     Returns (u, v, a) [N,3] at the last step in `dtype`; with return_info also the system.ExplicitResult (with `dt`)."""
     what = "explicit_dynamics_solver"
     mask, rec = _check_explicit(what, coords, elements, F, fixed, rho, E, nu, steps, dt, safety, material, amplitude,
                                 u0, v0, damping, record, energy_every)
     steps = int(steps)
+    if contact is not None:
+        contact = _sys.check_contact(what, contact, penalty, coords.shape[0], safety if dt is None else None)
+    if int(contact_every) < 0 or (int(contact_every) > 0 and not contact):
+        raise ValueError(f"{what}: contact_every must be >= 0 and needs contact surfaces, got {contact_every}")
     dev = _dev(device)
     cd = coords.to(device=dev, dtype=F64).contiguous()
     el = elements.to(device=dev, dtype=LONG).contiguous()
@@ -1042,11 +1051,14 @@ def explicit_dynamics_solver(coords, elements, F, fixed, rho, E, nu, steps, dt=N
         else:
             amps = [float(amplitude(k * dt)) for k in range(steps + 1)]
         Fd = F.to(device=dev, dtype=F64).reshape(-1).contiguous()
+        if contact:
+            xd.set_contact(contact, penalty, dt=dt)
         xd.start(u0, v0, Fd, amps[0])
         rdofs = None
         if rec is not None:
             rdofs = (rec.to(dev).unsqueeze(-1) * 3 + torch.arange(3, device=dev)).reshape(-1)
-        res = xd.run(steps, dt, Fd, amps, record=rdofs, energy_every=int(energy_every))
+        res = xd.run(steps, dt, Fd, amps, record=rdofs, energy_every=int(energy_every),
+                     contact_every=int(contact_every))
         if res.status != _sys.XD_OK:
             print(f"Explicit solver: status {res.status} at step {res.stop_step} (dt = {dt:.6e}); the state after "
                   f"{steps} steps is returned")

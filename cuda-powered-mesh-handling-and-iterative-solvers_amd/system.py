@@ -8,6 +8,7 @@ the coalesced COO of `subdivision.ipynb:118-139`, so `A @ p == compute_nodal_for
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import time
 from dataclasses import dataclass
@@ -2193,6 +2194,102 @@ class ExplicitResult:
     ext_power: torch.Tensor = None  # amp_n F . v_n
     ext_work: torch.Tensor = None   # amp_n F . u_n: the work of the load held at its current value (the potential of a
                                     # constant load; kinetic + strain - ext_work is then conserved without damping)
+    # with a contact set (ExplicitDynamics.set_contact): rows at the steps n with n % contact_every == 0 ...
+    t_contact: torch.Tensor = None       # [rows] (host): their times
+    reaction: torch.Tensor = None        # [rows, S, 3] (host): the force on each surface, -sum of what its nodes received
+    in_contact: torch.Tensor = None      # [rows, S] int64: nodes with a positive penetration
+    penetration: torch.Tensor = None     # [rows, S]: the largest penetration
+    # ... and on the energy steps
+    contact_energy: torch.Tensor = None  # sum k p^2 / 2, the potential of the normal forces
+    friction_power: torch.Tensor = None  # sum f_t . (v_n - w), the rate at which friction dissipates
+    surface_power: torch.Tensor = None   # sum f_c . w, the power the moving surfaces put in
+
+
+class RigidSurface:
+    """A rigid analytic surface for ExplicitDynamics.set_contact. kind "plane": `point` on it and `normal`
+    pointing into the side the body may occupy; "sphere": centre `point`, `radius`; "cylinder": infinite, `axis` through
+    `point`, `radius`. inside=True makes a sphere or cylinder a cavity that holds the body. friction: Coulomb mu >= 0.
+    The surface translates by `velocity` (a constant 3-vector: d(t) = velocity t) or by `displacement` (a callable of t
+    giving a 3-vector; its velocity during a step is the difference quotient over that step); its orientation is fixed.
+    nodes: the ids of the nodes that may touch it (default: all). Every ValueError is raised here or in check_contact,
+    before any device call."""
+
+    def __init__(self, kind, point, normal=None, axis=None, radius=None, inside=False, friction=0.0, velocity=None,
+                 displacement=None, nodes=None):
+        what = "RigidSurface"
+        if kind not in C.SURFACE_KINDS:
+            raise ValueError(f"{what}: unknown kind {kind!r} (supported: {', '.join(sorted(C.SURFACE_KINDS))})")
+        self.kind = kind
+        self.point = self._vec3(point, "point")
+        direction = {"plane": normal, "cylinder": axis, "sphere": None}[kind]
+        self.direction = (0.0, 0.0, 0.0)
+        if kind != "sphere":
+            name = "normal" if kind == "plane" else "axis"
+            if direction is None:
+                raise ValueError(f"{what}: a {kind} needs its {name}")
+            d = self._vec3(direction, name)
+            length = math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+            if not length > 0.0:
+                raise ValueError(f"{what}: the {name} must not be zero")
+            self.direction = tuple(x / length for x in d)
+        self.radius = 0.0
+        if kind != "plane":
+            if radius is None or not float(radius) > 0.0:
+                raise ValueError(f"{what}: a {kind} needs a radius > 0, got {radius}")
+            self.radius = float(radius)
+        self.inside = bool(inside) and kind != "plane"
+        if not float(friction) >= 0.0:
+            raise ValueError(f"{what}: friction must be >= 0, got {friction}")
+        self.friction = float(friction)
+        if velocity is not None and displacement is not None:
+            raise ValueError(f"{what}: give velocity or displacement, not both")
+        if displacement is not None and not callable(displacement):
+            raise ValueError(f"{what}: displacement must be a callable of t")
+        self.velocity = None if velocity is None else self._vec3(velocity, "velocity")
+        self.displacement = displacement
+        self.nodes = None if nodes is None else torch.as_tensor(nodes).to(torch.int64).reshape(-1).cpu()
+
+    @staticmethod
+    def _vec3(x, name):
+        v = [float(t) for t in (x.reshape(-1).tolist() if torch.is_tensor(x) else x)]
+        if len(v) != 3 or not all(math.isfinite(t) for t in v):
+            raise ValueError(f"RigidSurface: {name} must hold 3 finite values")
+        return tuple(v)
+
+    def offset(self, t):
+        """d(t) as 3 floats."""
+        if self.displacement is not None:
+            return self._vec3(self.displacement(t), "displacement(t)")
+        if self.velocity is not None:
+            return tuple(w * t for w in self.velocity)
+        return (0.0, 0.0, 0.0)
+
+    def step_velocity(self, t0, t1):
+        """The velocity of the step t0 -> t1: the constant one, else the difference quotient of d."""
+        if self.displacement is None:
+            return self.velocity or (0.0, 0.0, 0.0)
+        a, b = self.offset(t0), self.offset(t1)
+        return tuple((y - x) / (t1 - t0) for x, y in zip(a, b))
+
+
+def check_contact(what, surfaces, penalty, N, safety=None):
+    """The ValueErrors of a contact set -- no device call: at most 8 RigidSurface, node ids in [0, N), 0 < penalty < 4
+    and, where the caller takes dt = safety x the guaranteed stable step, penalty <= 4 (1 - safety^2), which keeps
+    omega dt <= 2. Returns the list of surfaces."""
+    surfaces = list(surfaces)
+    if len(surfaces) > C.XD_MAX_SURFACES:
+        raise ValueError(f"{what}: at most {C.XD_MAX_SURFACES} surfaces, got {len(surfaces)}")
+    for k, s in enumerate(surfaces):
+        if not isinstance(s, RigidSurface):
+            raise ValueError(f"{what}: surface {k} is not a RigidSurface")
+        if s.nodes is not None and s.nodes.numel() and (int(s.nodes.min()) < 0 or int(s.nodes.max()) >= N):
+            raise ValueError(f"{what}: surface {k} names a node outside [0, {N})")
+    if not 0.0 < float(penalty) < 4.0:
+        raise ValueError(f"{what}: penalty must lie in (0, 4), got {penalty}")
+    if safety is not None and float(penalty) > 4.0 * (1.0 - float(safety) ** 2) * (1.0 + 1e-12):   # 0.76 at 0.9 passes
+        raise ValueError(f"{what}: penalty {penalty} exceeds 4 (1 - safety^2) = {4.0 * (1.0 - float(safety) ** 2):.4g}, "
+                         f"the bound that keeps the step safety x the stable one within omega dt <= 2")
+    return surfaces
 
 
 @_scoped
@@ -2230,6 +2327,53 @@ class ExplicitDynamics:
                                        C.ptr(self.fixed_mask), self.damping, C.ptr(self.u), C.ptr(self.v),
                                        C.ptr(self.a), C.stream(dev), ctypes.byref(self.h)), "fem_xd_create")
         self.started = False
+        self._surfaces, self._word = [], None
+        self._t_base, self._n_base, self._t_dt = 0.0, 0, None   # the time reached is _t_base + _n_base * _t_dt
+
+    def time(self, k=0):
+        """The time k steps of the current dt after the state reached (kept on the host: surface motion continues
+        across runs and across changes of dt)."""
+        return self._t_base + (self._n_base + k) * self._t_dt if self._t_dt else self._t_base
+
+    def set_contact(self, surfaces, penalty=0.5, dt=None):
+        """Attach frictional penalty contact with up to 8 rigid surfaces (RigidSurface), or clear it with
+        None / []. penalty = kappa: the normal stiffness of node i is kappa m_i / dt^2 with the run's dt; 0 < kappa < 4,
+        and kappa <= 4 (1 - s^2) keeps a step of s x stable_dt() stable. Attach before start(): its a_0 then includes
+        the contact force at the surfaces' positions at the time reached, with the stiffness of `dt` (default 0.9 x
+        stable_dt(); the runs use their own dt)."""
+        what = "ExplicitDynamics.set_contact"
+        surfaces = check_contact(what, surfaces or [], penalty, self.N)
+        if dt is not None and not float(dt) > 0.0:
+            raise ValueError(f"{what}: dt must be > 0, got {dt}")
+        dev = self.device
+        if not surfaces:
+            C.check(self.lib.fem_xd_contact(self.h, 0, None, 0.0, 0.0, None, C.stream(dev)), "fem_xd_contact")
+            self._surfaces, self._word = [], None
+            return self
+        if dt is None:
+            dt = 0.9 * self.stable_dt()[0]
+            if not dt < float("inf"):
+                dt = 1.0
+        dt, t = float(dt), self.time()
+        rows = []
+        for s in surfaces:
+            d0 = s.offset(t)
+            rows += [float(C.SURFACE_KINDS[s.kind]), float(s.inside)] + [c + d for c, d in zip(s.point, d0)] + \
+                list(s.direction) + [s.radius, s.friction] + list(s.step_velocity(t, t + dt))
+        word = None
+        if any(s.nodes is not None for s in surfaces):
+            w = torch.zeros(max(self.N, 1), dtype=torch.uint8)
+            for k, s in enumerate(surfaces):
+                if s.nodes is None:
+                    w |= 1 << k
+                else:
+                    w[s.nodes] |= 1 << k
+            word = w.to(dev)
+        table = (ctypes.c_double * len(rows))(*rows)
+        C.check(self.lib.fem_xd_contact(self.h, len(surfaces), table, float(penalty), dt, C.ptr(word), C.stream(dev)),
+                "fem_xd_contact")
+        self._surfaces, self._word, self._contact_t0 = surfaces, word, t   # the word array lives as long as the set
+        return self
 
     def _vec(self, x, what, null=True):
         if x is None:
@@ -2262,6 +2406,7 @@ class ExplicitDynamics:
         C.check(self.lib.fem_xd_start(self.h, C.ptr(u0), C.ptr(v0), C.ptr(F), float(amp), C.stream(self.device)),
                 "fem_xd_start")
         self.started = True
+        self._t_base, self._n_base, self._t_dt = 0.0, 0, None
         return self
 
     def status(self):
@@ -2280,20 +2425,27 @@ class ExplicitDynamics:
         C.check(self.lib.fem_xd_info(self.h, w), "fem_xd_info")
         return int(w[0])
 
-    def run(self, steps, dt, F=None, amps=1.0, record=None, energy_every=0):
+    def run(self, steps, dt, F=None, amps=1.0, record=None, energy_every=0, contact_every=0):
         """`steps` steps of `dt` from the state reached, all enqueued at once (two launches per step). F [3N]: the load
         pattern (None: no load); amps: a number, or the load factors at the run's times -- steps + 1 values (t_n0 ..
         t_n0+steps; with `steps` values the last is held). record: dof indices whose u, v, a are kept per step;
         energy_every = m > 0: the energies at the steps n with n % m == 0 counted from the start. Consecutive runs
-        with the same dt continue the same trajectory bit for bit. Returns an ExplicitResult (reads the status words
-        back: one synchronisation at the end)."""
+        with the same dt continue the same trajectory bit for bit. With a contact set, contact_every = m > 0 keeps the
+        per-surface reaction, contact count and largest penetration at the steps n with n % m == 0, and the energy
+        steps also keep the penalty energy, the friction power and the surface power. Returns an ExplicitResult (reads
+        the status words back: one synchronisation at the end)."""
         what = "ExplicitDynamics.run"
         check_explicit_run(what, steps, dt)
         steps, dt, every = int(steps), float(dt), int(energy_every)
         if every < 0:
             raise ValueError(f"{what}: energy_every must be >= 0, got {energy_every}")
+        cevery = int(contact_every)
+        if cevery < 0 or (cevery > 0 and not self._surfaces):
+            raise ValueError(f"{what}: contact_every must be >= 0 and needs a contact set, got {contact_every}")
         if not self.started:
             self.start()
+        if dt != self._t_dt:   # the time so far is kept; steps are counted anew with this dt
+            self._t_base, self._n_base, self._t_dt = self.time(), 0, dt
         dev = self.device
         F = self._vec(F, "F")
         if isinstance(amps, (int, float)):
@@ -2318,7 +2470,35 @@ class ExplicitDynamics:
         rows = [n for n in range(n0, n0 + steps) if every and n % every == 0]
         en = torch.zeros((max(len(rows), 1), 4), dtype=F64, device=dev) if every else None
         amp_c = (ctypes.c_double * (steps + 1))(*al)
-        if self.n and steps:
+        S = len(self._surfaces)
+        crows = [n for n in range(n0, n0 + steps) if cevery and n % cevery == 0]
+        if S and self.n and steps:
+            times = [self.time(k) for k in range(steps + 2)]
+            t0 = self._contact_t0
+            base = [s.offset(t0) for s in self._surfaces]
+            off, vel = [], []
+            for k in range(steps + 1):
+                kv = min(k, steps - 1)   # the closing evaluation takes the last step's velocity
+                for s, b in zip(self._surfaces, base):
+                    off += [d - c for d, c in zip(s.offset(times[k]), b)]
+                    vel += list(s.step_velocity(times[kv], times[kv + 1]))
+            off_c, vel_c = (ctypes.c_double * len(off))(*off), (ctypes.c_double * len(vel))(*vel)
+            hist = torch.zeros((max(len(crows), 1), S, 5), dtype=F64, device=dev) if cevery else None
+            cen = torch.zeros((max(len(rows), 1), 3), dtype=F64, device=dev) if every else None
+            C.check(self.lib.fem_xd_run_contact(self.h, steps, dt, amp_c, C.ptr(F), nrec,
+                                                C.ptr(rdofs) if nrec else None, C.ptr(ru) if nrec else None,
+                                                C.ptr(rv) if nrec else None, C.ptr(ra) if nrec else None, every,
+                                                C.ptr(en), off_c, vel_c, cevery, C.ptr(hist), C.ptr(cen),
+                                                C.stream(dev)), "fem_xd_run_contact")
+            if cevery:
+                hc = hist[: len(crows)].cpu()
+                res.t_contact = torch.tensor([self.time(n - n0) for n in crows], dtype=F64)
+                res.reaction, res.penetration = hc[:, :, :3].clone(), hc[:, :, 4].clone()
+                res.in_contact = hc[:, :, 3].round().to(torch.int64)
+            if every:
+                ce = cen[: len(rows)].cpu()
+                res.contact_energy, res.friction_power, res.surface_power = ce[:, 0], ce[:, 1], ce[:, 2]
+        elif self.n and steps:
             C.check(self.lib.fem_xd_run(self.h, steps, dt, amp_c, C.ptr(F), nrec, C.ptr(rdofs) if nrec else None,
                                         C.ptr(ru) if nrec else None, C.ptr(rv) if nrec else None,
                                         C.ptr(ra) if nrec else None, every, C.ptr(en), C.stream(dev)), "fem_xd_run")
@@ -2332,6 +2512,7 @@ class ExplicitDynamics:
             res.t_energy = torch.tensor(rows, dtype=F64) * dt
             res.kinetic, res.strain, res.ext_power, res.ext_work = e[:, 0], e[:, 1], e[:, 2], e[:, 3]
         res.status, res.stop_step = self.status()
+        self._n_base += steps
         return res
 
     def close(self):

@@ -1178,6 +1178,43 @@ int fem_xd_force(fem_xd* h, const double* u, double* fint, fem_stream_t stream);
 int fem_xd_status(fem_xd* h, int64_t* out2, fem_stream_t stream);
 int fem_xd_info(fem_xd* h, int64_t* out4);
 
+/* ---- explicit dynamics: frictional penalty contact of the mesh nodes with up to FEM_XD_MAX_SURFACES rigid analytic
+ * surfaces that may translate (csrc/explicit.hip, k_xd_update_c). x = X + u_n is a node's position.
+ *   plane     g = (x - c) . n (n points into the side the body may occupy), nu = n
+ *   sphere    r = x - c, g = |r| - R, nu = r / |r|; inside (a cavity): g = R - |r|, nu = -r / |r|
+ *   cylinder  infinite, axis through c along n: r = (x - c) - ((x - c) . n) n, g and nu as for the sphere
+ * A node with |r| = 0, with g >= 0 or of zero mass gets no force. Normal force f_n = k p nu, p = max(0, -g),
+ * k = kappa m / dt^2 (m the node's lumped mass, dt the run's step). Friction, for the touched surfaces in index order:
+ * f_t = -min(mu |f_n|, m |vt| / sigma) vt / |vt|, vt the tangential part of v* - w, v* the new half-step velocity formed
+ * with every normal force and the friction of the surfaces before, w the surface velocity, sigma = dt c2 (dt / 2 in the
+ * first step after a start or a change of dt): friction never reverses sliding. Components on held dofs are dropped
+ * (v* is 0 there). The step's force is amp f_ext - f_int + f_c; everything else is as in fem_xd_run.
+ * fem_xd_contact: attach (nsurf = 1 .. 8) or clear (nsurf = 0) the contact set. surfaces (host, [nsurf, 13], read
+ *   during the call): kind (FEM_SURF_*), inside (0 / 1), c (3), n (3: unit normal or axis; unused for a sphere),
+ *   R (> 0; unused for a plane), mu >= 0, and the velocity (3) a fem_xd_start uses. 0 < kappa < 4; kappa <=
+ *   4 (1 - s^2) keeps omega dt <= 2 when dt = s x the bound of fem_xd_stable_dt. dt0 > 0: the step of the penalty
+ *   stiffness and friction cap at a fem_xd_start, whose a_0 then includes the contact force at the attached positions.
+ *   node_word (device, [N] uint8, nullable = every surface; it must outlive the set): bit s set -> the node may touch
+ *   surface s. With a set attached fem_xd_run is refused: fem_xd_run_contact takes the motion.
+ * fem_xd_run_contact: fem_xd_run with the set's motion. offsets, velocities (host, [nsteps + 1, nsurf, 3], read during
+ *   the call): surface s stands at c + offsets[k][s] with velocity velocities[k][s] during the run's step k; row nsteps
+ *   serves the closing evaluation of v_n, a_n. No launch is added outside history and energy steps and nothing
+ *   synchronises. history (device, [rows, nsurf, 5]): on the steps n with n % contact_every == 0 (n from the start; 0:
+ *   none) per surface the reaction on it (-sum of the contact force its nodes received, 3 values), the number of nodes
+ *   in contact and the largest penetration. contact_energies (device, [energy rows, 3]): on the energy steps the
+ *   penalty energy sum k p^2 / 2, the friction power sum f_t . (v_n - w) and the power of the moving surfaces
+ *   sum f_c . w. On those steps the kinetic energy and the two load terms of `energies` are summed per node, not per
+ *   dof: they may differ from fem_xd_run's in the last bits; u, v, a and the recorded rows of a run whose surfaces are
+ *   never touched are fem_xd_run's bit for bit. */
+enum { FEM_SURF_PLANE = 0, FEM_SURF_SPHERE = 1, FEM_SURF_CYLINDER = 2 };
+enum { FEM_XD_MAX_SURFACES = 8 };
+int fem_xd_contact(fem_xd* h, int64_t nsurf, const double* surfaces, double kappa, double dt0,
+                   const uint8_t* node_word, fem_stream_t stream);
+int fem_xd_run_contact(fem_xd* h, int64_t nsteps, double dt, const double* amps, const double* fext, int64_t nrec,
+                       const int64_t* rec_dofs, double* rec_u, double* rec_v, double* rec_a, int64_t energy_every,
+                       double* energies, const double* offsets, const double* velocities, int64_t contact_every,
+                       double* history, double* contact_energies, fem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
