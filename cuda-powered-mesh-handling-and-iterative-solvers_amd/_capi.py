@@ -29,7 +29,8 @@ TUNE_U2_HOLD, TUNE_U2_SMALL = 2048, 4096   # test-only knobs of the merged updat
 TUNE_MF_GATHER = 8192   # element-chunk operator: q summed by a gather launch instead of inside the merged update
 TUNE_PK_GV = 16384      # persistent schedule, small bs = 1 systems: the pipelined (Ghysels-Vanroose) iteration
 TUNE_PK_OFFDIAG = 32768  # persistent schedule, bs = 1: the diagonal kept on chip, off-diagonal values streamed
-TUNE_DEFAULT = 1 | 2 | 4 | 8 | 128 | TUNE_UPD1 | TUNE_PK_OFFDIAG
+TUNE_PK_DESC = 65536     # ... and each slice's header and delta list read from one record by scalar loads
+TUNE_DEFAULT = 1 | 2 | 4 | 8 | 128 | TUNE_UPD1 | TUNE_PK_OFFDIAG | TUNE_PK_DESC
 KIND_ELASTIC, KIND_POISSON, KIND_MASS = 0, 1, 2
 ISO_SUM, ISO_STACK, ISO_VOLUME, ISO_MASS = 0, 1, 2, 3
 MASS_SELL, MASS_DIAG = 0, 1   # include/fem355.h fem_mass_form
@@ -140,6 +141,8 @@ SIGNATURES = {
     "fem_pcg_uniform_slices": (_I, [_P, _L, _L, _P, _P, _P]),
     "fem_pcg_offdiag_slices": (_I, [_P, _P, _P, _P]),
     "fem_pcg_debug_offdiag": (_I, [_P, _P, _P]),
+    "fem_pcg_desc_slices": (_I, [_P, _P, _P]),
+    "fem_pcg_debug_desc": (_I, [_P, _P]),
     "fem_pcg_persist_build": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "fem_pcg_pipelined": (_I, [_P, ctypes.POINTER(_I)]),
     "fem_sell_sl_pattern": (_I, [_L, _P, _P, _I, _P, _P, _P, _P, _P]),

@@ -1928,6 +1928,8 @@ struct fem_pcg {
     int16_t* pk_oucol;    // delta lists (pucol's size), diagonal-free slices without their 0
     int32_t* pk_kd;       // [nslices] list index of the diagonal, -1: the slice kept its full rows
     double* pk_diag;      // [n] diagonal of the rows of diagonal-free slices (0 elsewhere)
+    PkDesc* pk_desc;      // [nslices] descriptor records of the stream (FEM_TUNE_PK_DESC; sell_pair.hpp PkDesc)
+    int pk_desc_on;       // this solve's k_sell_offdiag wrote them: persist_plan may pick a DESC build
     int pk_coop;          // launch through hipLaunchCooperativeKernel (fem_pcg_solve; FEM_TUNE_PK_COOP elsewhere)
     int pk_gv;            // pipelined persistent iteration (FEM_TUNE_PK_GV, pcg_persist_gv.hpp)
     double* gv_buf;       // its vectors: u, w, q, z, m[0], m[1] ([6 n])
@@ -2832,13 +2834,14 @@ struct PkBuild {
     bool od;     // diagonal-free value stream (FEM_TUNE_PK_OFFDIAG)
     const void* fn;
     size_t lds;  // dynamic LDS bytes of a launch
+    bool desc;   // slot headers and delta lists from per-slice records (FEM_TUNE_PK_DESC)
 };
 
 // a row's key and its template arguments come from the same parameters
-template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false, bool OD = false>
+template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false, bool OD = false, bool DESC = false>
 static PkBuild pk1_build() {
     return {DIST ? PKF_BS1_DIST : PKF_BS1, MAXS, PROF, GSC1, OVF, DIST, OD,
-            (const void*)k_pcg_persist<MAXS, PROF, GSC1, OVF, DIST, OD>, PK_LDS};
+            (const void*)k_pcg_persist<MAXS, PROF, GSC1, OVF, DIST, OD, DESC>, PK_LDS, DESC};
 }
 template <bool OVF, bool DIST>
 static PkBuild pk3_build() {
@@ -2875,6 +2878,12 @@ static const PkBuild PK_BUILDS[] = {
     pk1_build<PK_MAXS, true, false, false, false, true>(),
     pk1_build<PK_MAXS, false, true, true, false, true>(),
     pk1_build<PK_MAXS, false, false, true, false, true>(),
+    // the diagonal-free sc1 builds reading per-slice descriptor records, and the instrumented 7-slot one
+    pk1_build<1, false, true, false, false, true, true>(),
+    pk1_build<2, false, true, false, false, true, true>(),
+    pk1_build<4, false, true, false, false, true, true>(),
+    pk1_build<PK_MAXS, false, true, false, false, true, true>(),
+    pk1_build<PK_MAXS, true, true, false, false, true, true>(),
     // bs = 1, DIST: always sc1 gathers, never overflow; instrumented forms of the two larger ones only
     pk1_build<1, false, true, false, true>(),
     pk1_build<2, false, true, false, true>(),
@@ -2893,10 +2902,11 @@ static const PkBuild PK_BUILDS[] = {
     gv_build<2, true>(),
 };
 
-static const PkBuild* pk_find(PkFamily fam, int slots, bool prof, bool gsc1, bool ovf, bool dist, bool od) {
+static const PkBuild* pk_find(PkFamily fam, int slots, bool prof, bool gsc1, bool ovf, bool dist, bool od,
+                              bool desc = false) {
     for (const PkBuild& b : PK_BUILDS)
         if (b.fam == fam && b.slots == slots && b.prof == prof && b.gsc1 == gsc1 && b.ovf == ovf && b.dist == dist &&
-            b.od == od)
+            b.od == od && b.desc == desc)
             return &b;
     return nullptr;
 }
@@ -2942,7 +2952,8 @@ static PkPlan persist_plan(const fem_pcg* s, bool prof, bool gv) {
     prof = prof && !ovf;
     const bool small = pack >= 1 && pack <= 4 && !(s->tune & FEM_TUNE_PK_WIDE) && !prof && !ovf && gsc1;
     const int slots = !small ? PK_MAXS : pack == 1 ? 1 : pack == 2 ? 2 : 4;
-    return {pk_find(PKF_BS1, slots, prof, gsc1, ovf, false, s->pk_od != 0), pack};
+    const bool desc = s->pk_od && s->pk_desc_on && gsc1 && !ovf;   // (no DESC build with plain gathers or overflow)
+    return {pk_find(PKF_BS1, slots, prof, gsc1, ovf, false, s->pk_od != 0, desc), pack};
 }
 static PkPlan persist_plan(const fem_pcg* s, bool prof) { return persist_plan(s, prof, s->pk_gv && s->bs == 1); }
 
@@ -3188,7 +3199,7 @@ int fem_pcg_create(int64_t nrows, int bs, const int64_t* slice_ptr, const int32_
     }
     fem_pcg* s = new fem_pcg();
     s->tune = FEM_TUNE_REVERSE | FEM_TUNE_PAIR | FEM_TUNE_PK_SC1 | FEM_TUNE_PK_PACK | FEM_TUNE_PK_UNI | FEM_TUNE_UPD1 |
-              FEM_TUNE_PK_OFFDIAG;
+              FEM_TUNE_PK_OFFDIAG | FEM_TUNE_PK_DESC;
     s->nrows = nrows;
     s->bs = bs;
     s->nslices = cdiv(nrows, 64);
@@ -3478,6 +3489,7 @@ static int persist_setup_dist(fem_pcg* s);
 // have changed; the buffers are allocated once per context like pvals (the pattern of a context never changes).
 static int offdiag_build(fem_pcg* s) {
     s->pk_od = 0;
+    s->pk_desc_on = 0;
     if (!(s->tune & FEM_TUNE_PK_OFFDIAG) || !s->persist || s->bs != 1 || s->pd || s->pk_gv ||
         !(s->tune & FEM_TUNE_PK_UNI) || !s->puoff || !s->pucol)
         return FEM_OK;
@@ -3492,11 +3504,15 @@ static int offdiag_build(fem_pcg* s) {
         FEM_HIP(pool_alloc((void**)&s->pk_kd, sizeof(int32_t) * (size_t)s->nslices, s->stream, true));
         FEM_HIP(pool_alloc((void**)&s->pk_diag, sizeof(double) * (size_t)s->n, s->stream, true));
     }
+    const bool desc = (s->tune & FEM_TUNE_PK_DESC) != 0;   // the records ride on the same pass (64 bytes per slice)
+    if (desc && !s->pk_desc)
+        FEM_HIP(pool_alloc((void**)&s->pk_desc, sizeof(PkDesc) * (size_t)s->nslices, s->stream, true));
     hipLaunchKernelGGL(k_sell_offdiag, dim3((unsigned)cdiv(s->nslices, 4)), dim3(256), 0, s->stream, s->nslices,
                        s->nrows, s->slice_ptr, s->pvals, s->puoff, s->pucol, s->pk_ovals, s->pk_oucol, s->pk_kd,
-                       s->pk_diag);
+                       s->pk_diag, desc ? s->pk_desc : nullptr);
     FEM_LAUNCHED();
     s->pk_od = 1;
+    s->pk_desc_on = desc;
     return FEM_OK;
 }
 
@@ -3525,6 +3541,36 @@ int fem_pcg_offdiag_slices(fem_pcg* s, int64_t* od_slices, int64_t* nslices, int
     }
     *od_slices = c;
     *bytes = c * 64 * (int64_t)sizeof(double);   // one value per row of a diagonal-free slice
+    return FEM_OK;
+}
+
+// the started context's launches read records (a DESC build)
+static bool pk_runs_desc(const fem_pcg* s) {
+    if (!s->persist || !s->pk_od || s->bs != 1 || s->pd || s->pk_gv) return false;
+    const PkBuild* b = persist_plan(s, false, false).b;
+    return b && b->desc;
+}
+
+int fem_pcg_desc_slices(fem_pcg* s, int64_t* desc_slices, int64_t* nslices) {
+    *desc_slices = 0;
+    *nslices = s->nslices;
+    if (!pk_runs_desc(s) || s->nslices == 0) return FEM_OK;
+    std::vector<PkDesc> h((size_t)s->nslices);
+    FEM_HIP(hipMemcpyAsync(h.data(), s->pk_desc, sizeof(PkDesc) * h.size(), hipMemcpyDeviceToHost, s->stream));
+    FEM_HIP(hipStreamSynchronize(s->stream));
+    int64_t c = 0;
+    for (const PkDesc& d : h) c += ((d.w[3] >> 8) & 0xffu) != (uint32_t)PKD_LANE;
+    *desc_slices = c;
+    return FEM_OK;
+}
+
+int fem_pcg_debug_desc(fem_pcg* s, uint32_t* records) {
+    if (!pk_runs_desc(s)) {
+        set_error("fem_pcg_debug_desc: the started context reads no descriptor records");
+        return FEM_EARG;
+    }
+    FEM_HIP(hipMemcpyAsync(records, s->pk_desc, sizeof(PkDesc) * (size_t)s->nslices, hipMemcpyDeviceToHost, s->stream));
+    FEM_HIP(hipStreamSynchronize(s->stream));
     return FEM_OK;
 }
 
@@ -3716,6 +3762,7 @@ static PkArgs pk_args(const fem_pcg* s, const PkPlan& plan, int k, unsigned long
     a.diag = od ? s->pk_diag : nullptr;
     a.vals_full = s->pvals;
     a.ucol_full = uni ? s->pucol : nullptr;
+    a.desc = plan.b->desc ? s->pk_desc : nullptr;
     return a;
 }
 
@@ -4720,6 +4767,7 @@ void fem_pcg_destroy(fem_pcg* s) {
     pool_free(s->pk_v, s->stream);
     pool_free(s->pk_ovals, s->stream);
     pool_free(s->pk_oucol, s->stream);
+    pool_free(s->pk_desc, s->stream);
     pool_free(s->pk_kd, s->stream);
     pool_free(s->pk_diag, s->stream);
     pool_free(s->gv_buf, s->stream);

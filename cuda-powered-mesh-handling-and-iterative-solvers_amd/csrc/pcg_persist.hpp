@@ -38,6 +38,10 @@ constexpr int PK_U = 2;                  // pairs in flight per lane (4 spills t
 // up to four slots for 4 pairs (the instrumented builds keep PK_U there: their clock registers would spill)
 template <int MAXS, bool PROF>
 constexpr int pk_u() { return MAXS <= 1 ? 8 : (MAXS <= 4 && !PROF) ? 4 : PK_U; }
+// pairs in flight of a record slot (DESC builds): the one-slot build takes 4 there, since its 8-pair round beside the
+// 8-pair round of the slices read without a record spills into the SpMV (96 bytes of scratch per lane)
+template <int MAXS, bool PROF>
+constexpr int pk_u_rec() { return MAXS <= 1 ? 4 : pk_u<MAXS, PROF>(); }
 constexpr int PK_LINE = 32;              // unsigned words per 128-byte line
 // sync words (zeroed by fem_pcg_start; epochs continue across launches from PcgState::pk_epoch), in lines: [0, 8) group arrivals, 8 (unused), [9, 17) replicas of the
 // top counter (one per group),
@@ -219,6 +223,7 @@ struct PkArgs {
     const double* diag;
     const double* vals_full;   // the shared values and lists: the overflow slices of the OVF build read these
     const int16_t* ucol_full;
+    const PkDesc* desc;        // DESC build (FEM_TUNE_PK_DESC): one record per slice of the diagonal-free stream
 };
 
 // a product rounded on its own: the empty asm keeps the compiler from contracting it into a later add (an fma of
@@ -348,10 +353,15 @@ __device__ __forceinline__ void pk_publish_flag(const PkArgs& a, int Lg, unsigne
 // slots' rows sits in registers (dg[], loaded once per launch) where the other builds keep their own u (uo[]): that u
 // is w r, re-formed from w (LDS) and r (registers) as the same rounded product wherever it is needed (pk_mul_rn), so
 // the diagonal term costs no load and no gather, and every iterate keeps its bits.
-template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false, bool OD = false>
+// DESC (OD builds with sc1 gathers, no overflow): a slot's value base, width, kd and delta list come from the slice's
+// record (sell_pair.hpp PkDesc) by scalar loads instead of three dependent vector loads and the delta words of every
+// round. The record of the next slot is requested before the current slot's rounds, that of the sweep's first slot
+// before the u-flag wait (it does not depend on u). Slices of kind PKD_LANE run the OD build's path.
+template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false, bool OD = false, bool DESC = false>
 __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
     static_assert(!DIST || (GSC1 && !OVF), "distributed persistent PCG: sc1 gathers, no overflow build");
     static_assert(!(DIST && OD), "distributed persistent PCG: no diagonal-free stream");
+    static_assert(!DESC || (OD && GSC1 && !OVF), "descriptor records: the diagonal-free sc1 builds without overflow");
     unsigned long long pacc[PROF ? PK_NPROF : 1] = {};
     unsigned long long pt = 0, wspmv = 0;
     if constexpr (PROF) pt = __builtin_amdgcn_s_memtime();
@@ -532,6 +542,14 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
             const unsigned e = ebase + (unsigned)k + 1;
             // ---- wait for the u of the gather window (written by the previous update of this launch, or by the
             // distributed init above)
+            const bool rv = a.rev && ((it & 1) != 0);
+            PkRec rec = {};   // DESC: the record of the slot the sweep reads next
+            PkDescPtr dsp = nullptr;
+            if constexpr (DESC) {
+                dsp = (PkDescPtr)a.desc;
+                asm volatile("" : "+s"(dsp));   // (as pk_launder: no slot address is hoisted out of the k loop)
+                if (nreg > 0) rec = pk_rec_load(dsp, s0 + (rv ? nreg - 1 : 0));
+            }
             if (k > 0 || (DIST && a.init)) {
                 if (wv == 0) {
                     bool ok = true;
@@ -571,7 +589,6 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
             PK_MARK(0);
             // ---- v = A u over the own slices, d partial. Slots unrolled (register-resident state needs
             // compile-time indices); the empty asm keeps the compiler from interleaving slots (register blow-up)
-            const bool rv = a.rev && ((it & 1) != 0);
             unsigned long long tw0 = 0;
             if constexpr (PROF) tw0 = __builtin_amdgcn_s_memtime();
             // launder the matrix pointers every iteration: otherwise the per-slot addresses are hoisted out of the
@@ -587,6 +604,33 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
     (OD ? sell_row_pair_od<pk_u<MAXS, PROF>(), (MODE) == 3 ? 1 : (MODE)>(s0 + (j), lane, slp, cop, vap, uvp, uop, ucp,      \
                                        [&](double acc) { return acc + dg[OD ? (j) : 0] * PK_UO(j); })              \
         : sell_row_pair<pk_u<MAXS, PROF>(), MODE>(s0 + (j), lane, slp, cop, vap, uvp, olo, ohi, uop, ucp))
+// DESC: slot j from its record `rec`, the record of slot jn (the sweep's next; without one, slot j's again: a load
+// nobody waits for costs less than the register copies of a branch) requested first
+#define PK_SLOT_DESC(j, jn, more)                                                                                   \
+    {                                                                                                               \
+        const PkRec nx = pk_rec_load(dsp, s0 + ((more) ? (jn) : (j)));                                              \
+        double v;                                                                                                   \
+        if (rec.kind() != PKD_LANE)                                                                                 \
+            v = sell_row_pair_rec<pk_u_rec<MAXS, PROF>(), 1>(rec, (s0 + (j)) * 64, lane, vap, uvp,                  \
+                                                  [&](double acc) { return acc + dg[OD ? (j) : 0] * PK_UO(j); });   \
+        else                                                                                                        \
+            v = PK_ROW(1, j);                                                                                       \
+        if (j < PK_VL) vl[j * 64] = v; else vv[j] = v;                                                              \
+        rec = nx;                                                                                                   \
+    }
+#define PK_SPMV_DESC                                                                               \
+    if (!rv) {                                                                                     \
+        _Pragma("unroll") for (int j = 0; j < MAXS; ++j) {                                         \
+            if (j < nreg) PK_SLOT_DESC(j, j + 1, j + 1 < nreg)                                     \
+            asm volatile("" ::: "memory");                                                         \
+        }                                                                                          \
+    } else {                                                                                       \
+        _Pragma("unroll") for (int jj = 0; jj < MAXS; ++jj) {                                      \
+            const int j = MAXS - 1 - jj;                                                           \
+            if (j < nreg) PK_SLOT_DESC(j, j - 1, j > 0)                                            \
+            asm volatile("" ::: "memory");                                                         \
+        }                                                                                          \
+    }
 #define PK_SPMV(MODE)                                                                              \
     if (!rv) {                                                                                     \
         _Pragma("unroll") for (int j = 0; j < MAXS; ++j) {                                         \
@@ -609,12 +653,16 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
             // DIST: a workgroup whose gather window reaches other ranks reads the rows of other ranks past this GPU's
             // L2 (they arrive from other GPUs; the L2 may hold the previous iteration's copy), its own rank's rows
             // as usual (mode 3 picks per element)
-            if (DIST && ghost) {
+            if constexpr (DESC) {
+                PK_SPMV_DESC
+            } else if (DIST && ghost) {
                 PK_SPMV(3)
             } else {
                 PK_SPMV((GSC1 ? 1 : 0))
             }
 #undef PK_SPMV
+#undef PK_SPMV_DESC
+#undef PK_SLOT_DESC
 #undef PK_ROW
             if constexpr (PROF) {   // this wave's own SpMV time (results back: the v slots are written)
                 asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");

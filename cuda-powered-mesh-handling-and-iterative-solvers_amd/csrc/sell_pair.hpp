@@ -382,6 +382,21 @@ __device__ __forceinline__ double sell_row_pair_body(int64_t p0, int w, int base
     return acc;
 }
 
+// Per-slice descriptor record of the diagonal-free stream (FEM_TUNE_PK_DESC), written by k_sell_offdiag beside the
+// stream and read by k_pcg_persist<.., DESC = true> with scalar loads: everything the SpMV of a slice needs before its
+// first value load, at an address that depends on the slice index alone. 12 words: the value base p0 (words 0-1), the
+// streamed width (2), word 3 = kd (bits 0-7, signed; -1: nothing left out) | kind (bits 8-15) | the delta of an odd
+// width's last entry (bits 16-31), then the streamed delta list two per word, zero-padded to PKD_CAP entries.
+// Kinds: PKD_OD a slice-uniform slice without its diagonal, PKD_FULL a slice-uniform slice that kept its full rows,
+// PKD_LANE per-lane deltas or a list past PKD_CAP -- such a slice is read as before (uoff, the lists, kd's list slot).
+constexpr int PKD_CAP = 16;
+enum { PKD_OD = 0, PKD_FULL = 1, PKD_LANE = 2 };
+struct alignas(64) PkDesc {
+    uint32_t w[4 + PKD_CAP / 2];
+    uint32_t pad[4];   // (never written or read: the stride keeps a record inside one 64-byte line)
+};
+static_assert(sizeof(PkDesc) == 64, "persistent PCG: one 64-byte descriptor record per slice");
+
 // Diagonal-free value stream of the persistent schedule (FEM_TUNE_PK_OFFDIAG), private to one solver context. A
 // slice-uniform slice whose delta list holds delta 0 at list index kd stores its other w - 1 list entries, in list
 // order, lane-paired as a slice of width w - 1 at the slice's own base (slice_ptr is kept, so one pointer array
@@ -397,7 +412,8 @@ __attribute__((unused)) static __global__ void __launch_bounds__(256) k_sell_off
                                                              const int32_t* __restrict__ uoff,
                                                              const int16_t* __restrict__ ucol,
                                                              double* __restrict__ ovals, int16_t* __restrict__ oucol,
-                                                             int32_t* __restrict__ kd, double* __restrict__ diag) {
+                                                             int32_t* __restrict__ kd, double* __restrict__ diag,
+                                                             PkDesc* __restrict__ desc) {
     const int64_t s = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int l = threadIdx.x & 63;
     if (s >= nslices) return;   // wave-uniform
@@ -413,6 +429,23 @@ __attribute__((unused)) static __global__ void __launch_bounds__(256) k_sell_off
     if (l == 0) {
         kd[s] = kdv;
         if (uo >= 0) oucol[uo + 2 * w - 1] = (int16_t)kdv;
+    }
+    if (desc) {   // the slice's record (PkDesc): the header by lane 0, one word of two streamed deltas per lane
+        const int ws = w - (kdv >= 0);
+        const int kind = (uo < 0 || ws > PKD_CAP) ? PKD_LANE : kdv >= 0 ? PKD_OD : PKD_FULL;
+        auto sd = [&](int k) {   // streamed list entry k (the list without its 0), 0 past the list
+            return (kind != PKD_LANE && k < ws) ? (int)ucol[uo + k + (kdv >= 0 && k >= kdv)] : 0;
+        };
+        uint32_t* rec = reinterpret_cast<uint32_t*>(desc + s);
+        if (l < PKD_CAP / 2) rec[4 + l] = (uint32_t)(uint16_t)sd(2 * l) | ((uint32_t)(uint16_t)sd(2 * l + 1) << 16);
+        if (l == 0) {
+            const int tail = (ws & 1) ? sd(ws - 1) : 0;
+            rec[0] = (uint32_t)((uint64_t)p0 & 0xffffffffu);
+            rec[1] = (uint32_t)((uint64_t)p0 >> 32);
+            rec[2] = (uint32_t)ws;
+            rec[3] = (uint32_t)(uint8_t)(int8_t)(kind == PKD_LANE ? -1 : kdv) | ((uint32_t)kind << 8) |
+                     ((uint32_t)(uint16_t)tail << 16);
+        }
     }
     if (kdv < 0) {
         for (int k = 0; k < w; ++k) ovals[p0 + 64 * k + l] = pvals[p0 + 64 * k + l];
@@ -539,6 +572,82 @@ __device__ __forceinline__ double sell_row_pair_od(int64_t s, int lane, const in
         return sell_row_pair_od_body<U, SC1>(p0, w - (kdv >= 0), base, lane, ucol + uo, vals, x, 0, 0, kdv, diag);
     }
     return sell_row_pair_body<U, SC1, false>(p0, w, base, lane, cols, nullptr, vals, x, 0, 0);
+}
+
+// A slice's record held in scalar registers: read through the constant address space (the records are written before
+// the launch and never during it), so the loads are scalar loads that touch neither a vector register nor the
+// vector-memory counter, and may be requested long before their slice's turn.
+typedef uint32_t pk_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t pk_u32x8 __attribute__((ext_vector_type(8)));
+typedef const __attribute__((address_space(4))) PkDesc* PkDescPtr;
+struct PkRec {
+    pk_u32x4 h;
+    pk_u32x8 d;
+    __device__ __forceinline__ int kind() const { return (int)((h.w >> 8) & 0xffu); }
+};
+__device__ __forceinline__ PkRec pk_rec_load(PkDescPtr desc, int s) {
+    typedef const __attribute__((address_space(4))) pk_u32x4* P4;
+    typedef const __attribute__((address_space(4))) pk_u32x8* P8;
+    P4 q = reinterpret_cast<P4>(desc + s);
+    PkRec r;
+    r.h = q[0];
+    r.d = *reinterpret_cast<P8>(q + 1);
+    return r;
+}
+
+// y_row of a record slice (PKD_OD / PKD_FULL): sell_row_pair_od_body's sum -- the same terms `acc += a * b` in list
+// order, the diagonal term before streamed entry kd -- with the value base, the width, kd and every delta taken from
+// the record's scalar registers. A round's value loads and gathers depend on no earlier load, so they are issued
+// together and the wave waits once per round, before the round's first product. The delta words move down by U after
+// each round (scalar moves), which keeps every register index a constant. Every address is written as a wave-uniform
+// 64-bit base (value row of the round, x + first row of the slice + delta: scalar arithmetic) plus the lane's 32-bit
+// offset; the compiler turns that into two per-lane bases per slice and one 64-bit add per load, and keeps no
+// per-lane address across the slots (written per lane as in sell_row_pair_od_body, the 7-slot build spilled 84 bytes).
+// row0: the slice's first row.
+template <int U, int SC1, class Diag>
+__device__ __forceinline__ double sell_row_pair_rec(const PkRec& rc, int row0, int lane, const double* __restrict__ vals,
+                                                    const double* __restrict__ x, const Diag& diag) {
+    const int64_t p0 = (int64_t)((uint64_t)rc.h.x | ((uint64_t)rc.h.y << 32));
+    const int w1 = (int)rc.h.z;
+    const int kd = (int)(int8_t)(rc.h.w & 0xffu);
+    const int dtail = (int)(int16_t)(rc.h.w >> 16);
+    const int np = w1 >> 1;
+    const double2* v2 = reinterpret_cast<const double2*>(vals + p0);
+    const double* xb = x + row0;
+    const unsigned ul = (unsigned)lane;
+    uint32_t d[PKD_CAP / 2] = {rc.d.s0, rc.d.s1, rc.d.s2, rc.d.s3, rc.d.s4, rc.d.s5, rc.d.s6, rc.d.s7};
+    double acc = 0.0;
+#pragma nounroll
+    for (int j0 = 0; j0 < np; j0 += U) {
+        double2 vv[U];
+        double x0[U], x1[U];
+#pragma unroll
+        for (int j = 0; j < U; ++j) vv[j] = (j0 + j < np) ? (v2 + 64 * (j0 + j))[ul] : double2{0.0, 0.0};
+#pragma unroll
+        for (int j = 0; j < U; ++j) {
+            const int lo = (int)(int16_t)(d[j] & 0xffffu), hi = (int)(int16_t)(d[j] >> 16);
+            x0[j] = (j0 + j < np) ? ldx<SC1>((xb + lo) + ul) : 0.0;
+            x1[j] = (j0 + j < np) ? ldx<SC1>((xb + hi) + ul) : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < U; ++j)
+            if (j0 + j < np) {
+                const int k = 2 * (j0 + j);
+                if (k == kd) acc = diag(acc);
+                acc += vv[j].x * x0[j];
+                if (k + 1 == kd) acc = diag(acc);
+                acc += vv[j].y * x1[j];
+            }
+#pragma unroll
+        for (int i = 0; i + U < PKD_CAP / 2; ++i) d[i] = d[i + U];
+    }
+    if (w1 & 1) {
+        const double xt = ldx<SC1>((xb + dtail) + ul);
+        if (kd == w1 - 1) acc = diag(acc);
+        acc += (vals + p0 + (int64_t)np * 128)[ul] * xt;
+    }
+    if (kd == w1) acc = diag(acc);
+    return acc;
 }
 
 // uoff / ucol (nullable): the slice-uniform deltas of k_sell_uniform

@@ -1858,6 +1858,20 @@ class PcgRunner:
         C.check(self.lib.fem_pcg_debug_offdiag(self.h, C.ptr(A.g.rowptr), C.ptr(out)), "fem_pcg_debug_offdiag")
         return out
 
+    def desc_slices(self):
+        """(slices the persistent launches read from descriptor records, slices) of the started context
+        (include/fem355.h FEM_TUNE_PK_DESC); (0, slices) when its build reads no records."""
+        c, n = ctypes.c_int64(), ctypes.c_int64()
+        C.check(self.lib.fem_pcg_desc_slices(self.h, ctypes.byref(c), ctypes.byref(n)), "fem_pcg_desc_slices")
+        return c.value, n.value
+
+    def debug_desc_records(self):
+        """Test-only: the started context's descriptor records, an int32 tensor [slices, 16] on the host (word layout:
+        csrc/sell_pair.hpp PkDesc)."""
+        out = torch.empty((max(self.A.g.slice_ptr.numel() - 1, 0), 16), dtype=torch.int32)
+        C.check(self.lib.fem_pcg_debug_desc(self.h, ctypes.c_void_p(out.data_ptr())), "fem_pcg_debug_desc")
+        return out
+
     def pipelined(self):
         """True when the started context runs the pipelined persistent iteration (tune |= TUNE_PK_GV; bs = 1, single
         GPU, PCG mode, at most 2 slices per wave -- include/fem355.h FEM_TUNE_PK_GV)."""

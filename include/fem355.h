@@ -464,6 +464,14 @@ int fem_pcg_offdiag_slices(fem_pcg* s, int64_t* od_slices, int64_t* nslices, int
  * context's diagonal-free stream and its dense diagonal; rowptr: the pattern's CSR row pointers (device, int32).
  * FEM_EARG when the context reads no such stream */
 int fem_pcg_debug_offdiag(fem_pcg* s, const int32_t* rowptr, double* vals);
+/* [sync] after fem_pcg_start: the slices the persistent launches read from descriptor records (FEM_TUNE_PK_DESC: every
+ * slice-uniform slice of at most 16 streamed entries) and the slice count; 0 when the context's build reads none */
+int fem_pcg_desc_slices(fem_pcg* s, int64_t* desc_slices, int64_t* nslices);
+/* [sync, debug, test-only] the started context's descriptor records copied to the host: 16 words per slice -- value
+ * base (words 0-1), streamed width (2), kd (bits 0-7, signed) | kind (bits 8-15: 0 diagonal-free, 1 full rows,
+ * 2 read without a record) | an odd width's last delta (bits 16-31) (3), the streamed deltas two per word, zero-padded
+ * (4-11); words 12-15 are unused. FEM_EARG when the context reads no records */
+int fem_pcg_debug_desc(fem_pcg* s, uint32_t* records);
 /* ------------------------------------------------------------------ solver layout
  * The matrix stored straight in the layout the PCG schedules read, so a solve converts nothing and the matrix is
  * resident once. bs = 1: lane-paired SELL entries (entry k of lane l of a slice of width w at 128 (k / 2) + 2 l + k % 2,
@@ -572,14 +580,22 @@ int fem_enforce_constraints(double* x, double* r, int64_t n, int order, int64_t 
                             int64_t G, const int64_t* r3_ptr, const int64_t* r3_master, const double* r3_wsum,
                             const int64_t* r3_slave, const double* r3_w, fem_stream_t stream);
 /* tuning flags (default FEM_TUNE_REVERSE | FEM_TUNE_PAIR | FEM_TUNE_PK_SC1 | FEM_TUNE_PK_PACK | FEM_TUNE_PK_UNI |
- * FEM_TUNE_UPD1 | FEM_TUNE_PK_OFFDIAG): the SpMV of every schedule sweeps each XCD's slice range backwards on
+ * FEM_TUNE_UPD1 | FEM_TUNE_PK_OFFDIAG | FEM_TUNE_PK_DESC): the SpMV of every schedule sweeps each XCD's slice range backwards on
  * odd iterations, so the matrix tail read last (still in the MI355X's 256 MB memory-side cache) is read first by
  * the next sweep: 67 -> 57 us per SpMV on the 10M Poisson matrix. Results depend on the flags only through the
  * order of the per-block p.q partials (deterministic for a given flag set). */
 enum { FEM_TUNE_REVERSE = 1, FEM_TUNE_PAIR = 2, FEM_TUNE_PK_SC1 = 4, FEM_TUNE_PK_PACK = 8, FEM_TUNE_C1F = 16,
        FEM_TUNE_PK_COOP = 32, FEM_TUNE_DIST_FINE = 64, FEM_TUNE_PK_UNI = 128, FEM_TUNE_PK_WIDE = 256,
        FEM_TUNE_DIST_DROP = 512, FEM_TUNE_UPD1 = 1024, FEM_TUNE_U2_HOLD = 2048, FEM_TUNE_U2_SMALL = 4096,
-       FEM_TUNE_MF_GATHER = 8192, FEM_TUNE_PK_GV = 16384, FEM_TUNE_PK_OFFDIAG = 32768 };
+       FEM_TUNE_MF_GATHER = 8192, FEM_TUNE_PK_GV = 16384, FEM_TUNE_PK_OFFDIAG = 32768,
+       FEM_TUNE_PK_DESC = 65536 };
+/* FEM_TUNE_PK_DESC (default; needs FEM_TUNE_PK_OFFDIAG and FEM_TUNE_PK_SC1, not the overflow build): the pass that
+ * writes the diagonal-free stream also writes one 64-byte record per slice -- value base, streamed width, the
+ * diagonal's list position and the slice's delta list -- and the kernel reads a slot's record with scalar loads, one
+ * slot ahead (the sweep's first slot before the u-flag wait), instead of three dependent wave-uniform vector loads per
+ * slot and the delta words of every round. A round's value loads and u gathers then leave together. The same products
+ * in the same order: bit-identical iterates. Slices with per-lane deltas or more than 16 streamed entries are read as
+ * before. fem_pcg_desc_slices reports how many slices run from records. */
 /* FEM_TUNE_PK_OFFDIAG (default): persistent schedule, bs = 1, single GPU, not the pipelined build -- fem_pcg_start
  * writes a context-private copy of the paired values in which every slice-uniform slice whose delta list holds 0
  * leaves its diagonal out (width w - 1 at the slice's own slice_ptr base, sell_pair.hpp k_sell_offdiag), and the
