@@ -125,11 +125,8 @@ __global__ void __launch_bounds__(256) k_iso_geom(const double* __restrict__ X, 
         if (Jout)
             for (int t = 0; t < 9; ++t) Jout[e * 9 + t] = J[t];
         if (!Gout && !Bout) continue;
-        const double c00 = J[4] * J[8] - J[5] * J[7], c01 = J[5] * J[6] - J[3] * J[8], c02 = J[3] * J[7] - J[4] * J[6];
-        const double id = 1.0 / (J[0] * c00 + J[1] * c01 + J[2] * c02);
-        const double Ji[9] = {c00 * id, (J[2] * J[7] - J[1] * J[8]) * id, (J[1] * J[5] - J[2] * J[4]) * id,
-                              c01 * id, (J[0] * J[8] - J[2] * J[6]) * id, (J[2] * J[3] - J[0] * J[5]) * id,
-                              c02 * id, (J[1] * J[6] - J[0] * J[7]) * id, (J[0] * J[4] - J[1] * J[3]) * id};
+        double Ji[9];
+        inv3(J, Ji);
         const int d3 = 3 * npe;
         if (Bout)
             for (int t = 0; t < 6 * d3; ++t) Bout[e * 6 * d3 + t] = 0.0;
@@ -157,14 +154,13 @@ __global__ void __launch_bounds__(256) k_iso_geom(const double* __restrict__ X, 
 
 // ---------------------------------------------------------------- packed symmetric element matrices (bs = 3)
 // K_e = sum_q B_q^T D B_q is symmetric: the internal assembly path stores only its upper 3x3 blocks (a <= b), row-major
-// over the upper triangle (block index ke_sym_blk(a, b)), 9 doubles each, padded to an even count per element
-// (16-byte aligned elements): c3d10 496 doubles instead of 900, c3d8 324 of 576, c3d6 190 of 324, c3d4 78 of 144.
+// over the upper triangle (block index sym_blk(npe, a, b) of element.hpp), 9 doubles each, padded to an even count per
+// element (16-byte aligned elements): c3d10 496 doubles instead of 900, c3d8 324 of 576, c3d6 190 of 324, c3d4 78 of
+// 144.
 __host__ __device__ constexpr int ke_sym_nb(int npe) { return npe * (npe + 1) / 2; }
 __host__ __device__ constexpr int ke_sym_stride(int npe) { return (9 * ke_sym_nb(npe) + 1) & ~1; }
-__host__ __device__ constexpr int ke_sym_blk(int npe, int a, int b) { return a * npe - a * (a - 1) / 2 + (b - a); }
 
 // ---------------------------------------------------------------- isoparametric solids (wave per element)
-constexpr int ISO_MAX_IP = 32;
 constexpr int ISO_IPC = 16;   // points whose geometry is staged in LDS at once
 
 // LDS hand-off between the lanes of one wave (program order for the compiler; a wave's LDS operations run in order)
@@ -857,7 +853,7 @@ struct KeRowLane {
 // 9 + r * 3 + c] += the row's K_e block rows over its incidences in ascending (incidence, b) order (acc zeroed by the
 // caller). Scratch: slot_s / koff_s / eid_s [64] of this wave.
 // PK: Ke holds the packed upper blocks (ke_sym_stride(NPE) doubles per element): block (a, b) of the row's element
-// node a is read from block ke_sym_blk(a, b) for a <= b and as the transpose of block ke_sym_blk(b, a) otherwise --
+// node a is read from block sym_blk(NPE, a, b) for a <= b and as the transpose of block sym_blk(NPE, b, a) otherwise --
 // the same values in the same (incidence, b) order, so the sums equal the full-K_e sums whenever the full K_e's lower
 // blocks are the transposes of its upper ones (c3d10: mirrored by k_iso_ke, bit-identical)
 // An element listing one node twice, seen by the lanes (u, b) = u NPE + b holding node b of incidence u: 1 in the lane
@@ -932,7 +928,7 @@ __device__ __forceinline__ void ke_row3(const KeRowLane<NPE>& L, const double* _
 #pragma unroll
                     for (int m = 0; m < NL; ++m) {
                         const int b = L.vb[m];
-                        const int off = a <= b ? ke_sym_blk(NPE, a, b) * 9 + L.vo[m] : ke_sym_blk(NPE, b, a) * 9 + vt[m];
+                        const int off = a <= b ? sym_blk(NPE, a, b) * 9 + L.vo[m] : sym_blk(NPE, b, a) * 9 + vt[m];
                         v[u][m] = (u < nu && L.vv[m]) ? Ke[base + off] : 0.0;
                     }
                 } else {

@@ -21,16 +21,14 @@
 
 namespace fem {
 
-constexpr int GEO_MAX_IP = 32;   // the ISO_MAX_IP of assemble.hip: the same tables feed both
-
 template <int NPE, bool HAS_U>
 __global__ void __launch_bounds__(256) k_geo_s(const double* __restrict__ X, const int64_t* __restrict__ conn,
                                                int64_t M, const double* __restrict__ U, Lame L,
                                                const double* __restrict__ S0, const double* __restrict__ dN,
                                                const double* __restrict__ w, int n_ip, double* __restrict__ Gs,
                                                uint8_t* __restrict__ bad) {
-    __shared__ double dn_s[GEO_MAX_IP * NPE * 3];
-    __shared__ double w_s[GEO_MAX_IP];
+    __shared__ double dn_s[ISO_MAX_IP * NPE * 3];
+    __shared__ double w_s[ISO_MAX_IP];
     for (int t = threadIdx.x; t < n_ip * NPE * 3; t += 256) dn_s[t] = dN[t];
     for (int t = threadIdx.x; t < n_ip; t += 256) w_s[t] = w[t];
     __syncthreads();
@@ -122,7 +120,7 @@ __global__ void __launch_bounds__(256) k_geo_s(const double* __restrict__ X, con
                 const double t2 = T[6] * d[0] + T[7] * d[1] + T[8] * d[2];
 #pragma unroll
                 for (int a = 0; a <= b; ++a)
-                    m[a * NPE - a * (a - 1) / 2 + (b - a)] += dq[a * 3] * t0 + dq[a * 3 + 1] * t1 + dq[a * 3 + 2] * t2;
+                    m[sym_blk(NPE, a, b)] += dq[a * 3] * t0 + dq[a * 3 + 1] * t1 + dq[a * 3 + 2] * t2;
             }
         }
         if (degenerate) bad[e] = 1;
@@ -134,7 +132,7 @@ __global__ void __launch_bounds__(256) k_geo_s(const double* __restrict__ X, con
             for (int h = 0; h < 2; ++h) {
                 const int i = 2 * p + h, a = i / NPE, b = i - NPE * (i / NPE);
                 const int lo = a < b ? a : b, hi = a < b ? b : a;
-                v2[h] = m[lo * NPE - lo * (lo - 1) / 2 + (hi - lo)];
+                v2[h] = m[sym_blk(NPE, lo, hi)];
             }
             out[p] = make_double2(v2[0], v2[1]);
         }
@@ -169,8 +167,8 @@ int fem_geo_scalar(const double* coords, const int64_t* conn, int64_t M, int npe
         set_error("fem_geo_scalar: coords, conn, dN, w, Gs and bad may not be NULL");
         return FEM_EARG;
     }
-    if (n_ip < 1 || n_ip > GEO_MAX_IP) {
-        set_error("fem_geo_scalar: n_ip = %d out of range [1, %d]", n_ip, GEO_MAX_IP);
+    if (n_ip < 1 || n_ip > ISO_MAX_IP) {
+        set_error("fem_geo_scalar: n_ip = %d out of range [1, %d]", n_ip, ISO_MAX_IP);
         return FEM_EARG;
     }
     if (npe != 4 && npe != 6 && npe != 8 && npe != 10) {

@@ -7,9 +7,9 @@
 //                    svk          f_a = V F S g_a, S = lam tr(E) I + 2 mu E, E = (H + H^T + H^T H) / 2
 //                    neo_hookean  f_a = V P g_a, P = mu (F - F^-T) + lam ln J F^-T
 //                  with H = sum_a u_a (x) g_a (formed from the differences u_b - u_0, so a translation adds nothing),
-//                  F = I + H; det F and the cofactors of F in the compensated forms of nonlinear.hip. An element with
-//                  det F <= 0 or a degenerate reference element adds zero force and lowers the status word to the
-//                  step; on energy steps the workgroup's strain energy goes to epart[chunk].
+//                  F = I + H; det F and the cofactors of F in the compensated forms dop / dot3c of element.hpp. An
+//                  element with det F <= 0 or a degenerate reference element adds zero force and lowers the status
+//                  word to the step; on energy steps the workgroup's strain energy goes to epart[chunk].
 //   k_xd_update  : per dof, f_int = the node's slots in ascending chunk order, then
 //                    v_{n+1/2} = ((1 - alpha dt/2) v_{n-1/2} + dt (amp_n f_ext - f_int) / m) / (1 + alpha dt/2)
 //                    u_{n+1}   = u_n + dt v_{n+1/2}
@@ -40,29 +40,6 @@ namespace fem {
 constexpr int XD_BLOCK = 256;
 constexpr unsigned long long XD_NONE = ~0ull;
 constexpr int XD_NE = 4;   // values per energy row: kinetic, strain, external power, external work term
-
-// a b - c d and x0 y0 + x1 y1 + x2 y2 with the products' rounding errors carried along (nl_dop / nl_dot3c of
-// nonlinear.hip): det F and the cofactors of F keep the digits the plain forms lose when |F| >> det F
-__device__ __forceinline__ double xd_dop(double a, double b, double c, double d) {
-#pragma clang fp contract(off)
-    const double w = c * d;
-    const double e = fma(-c, d, w);
-    const double f = fma(a, b, -w);
-    return f + e;
-}
-
-__device__ __forceinline__ double xd_dot3c(double x0, double y0, double x1, double y1, double x2, double y2) {
-#pragma clang fp contract(off)
-    const double p0 = x0 * y0, p1 = x1 * y1, p2 = x2 * y2;
-    const double e0 = fma(x0, y0, -p0), e1 = fma(x1, y1, -p1), e2 = fma(x2, y2, -p2);
-    const double s = p0 + p1;
-    const double b1 = s - p0;
-    const double t1 = (p0 - (s - b1)) + (p1 - b1);
-    const double s2 = s + p2;
-    const double b2 = s2 - s;
-    const double t2 = (s - (s2 - b2)) + (p2 - b2);
-    return s2 + ((t1 + t2) + ((e0 + e1) + e2));
-}
 
 // signed det of the edge matrix and the unscaled cofactors c_1..c_3 (g_b = c_b / det), as mf_element forms them
 __device__ __forceinline__ double xd_cofactors(const double xc[4][3], double c[4][3]) {
@@ -129,10 +106,10 @@ __device__ __forceinline__ bool xd_element(const double xc[4][3], const double u
 #pragma unroll
             for (int j = 0; j < 3; ++j) F[i][j] = (i == j ? 1.0 : 0.0) + H[i][j];
         double Cf[3][3];   // cofactors of F
-        Cf[0][0] = xd_dop(F[1][1], F[2][2], F[1][2], F[2][1]);
-        Cf[0][1] = xd_dop(F[1][2], F[2][0], F[1][0], F[2][2]);
-        Cf[0][2] = xd_dop(F[1][0], F[2][1], F[1][1], F[2][0]);
-        const double J = xd_dot3c(F[0][0], Cf[0][0], F[0][1], Cf[0][1], F[0][2], Cf[0][2]);
+        Cf[0][0] = dop(F[1][1], F[2][2], F[1][2], F[2][1]);
+        Cf[0][1] = dop(F[1][2], F[2][0], F[1][0], F[2][2]);
+        Cf[0][2] = dop(F[1][0], F[2][1], F[1][1], F[2][0]);
+        const double J = dot3c(F[0][0], Cf[0][0], F[0][1], Cf[0][1], F[0][2], Cf[0][2]);
         ok = ok && J > 0.0;   // false for a NaN as well
         const double Js = ok ? J : 1.0;
         double P[3][3];   // first Piola-Kirchhoff stress
@@ -158,12 +135,12 @@ __device__ __forceinline__ bool xd_element(const double xc[4][3], const double u
                 w = V * (0.5 * lam * trE * trE + mu * ((Ed[0] * Ed[0] + Ed[1] * Ed[1] + Ed[2] * Ed[2]) +
                                                        2.0 * (Ed[3] * Ed[3] + Ed[4] * Ed[4] + Ed[5] * Ed[5])));
         } else {
-            Cf[1][0] = xd_dop(F[0][2], F[2][1], F[0][1], F[2][2]);
-            Cf[1][1] = xd_dop(F[0][0], F[2][2], F[0][2], F[2][0]);
-            Cf[1][2] = xd_dop(F[0][1], F[2][0], F[0][0], F[2][1]);
-            Cf[2][0] = xd_dop(F[0][1], F[1][2], F[0][2], F[1][1]);
-            Cf[2][1] = xd_dop(F[0][2], F[1][0], F[0][0], F[1][2]);
-            Cf[2][2] = xd_dop(F[0][0], F[1][1], F[0][1], F[1][0]);
+            Cf[1][0] = dop(F[0][2], F[2][1], F[0][1], F[2][2]);
+            Cf[1][1] = dop(F[0][0], F[2][2], F[0][2], F[2][0]);
+            Cf[1][2] = dop(F[0][1], F[2][0], F[0][0], F[2][1]);
+            Cf[2][0] = dop(F[0][1], F[1][2], F[0][2], F[1][1]);
+            Cf[2][1] = dop(F[0][2], F[1][0], F[0][0], F[1][2]);
+            Cf[2][2] = dop(F[0][0], F[1][1], F[0][1], F[1][0]);
             const double lnJ = log(Js);
             // P = mu F + (lam ln J - mu) F^-T, F^-T = Cf / J; mu (F - F^-T) is formed entry by entry so that the
             // two cancel at F = I

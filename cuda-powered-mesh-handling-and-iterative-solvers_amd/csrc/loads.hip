@@ -1,14 +1,13 @@
-// Distributed loads on gfx950: body force, thermal strain and surface pressure / traction turned into nodal forces,
-// and the stress recovery that subtracts the thermal strain. No reference function exists for any of
-// them (the reference's solvers take a finished force array): the formulas are the consistent ones for the element
-// matrices this library already forms.
+// Distributed loads on gfx950: body force, thermal strain and surface pressure / traction turned into nodal forces
+// (the stress recovery that subtracts the thermal strain is stress.hip's). No reference function exists for
+// any of them (the reference's solvers take a finished force array): the formulas are the consistent ones for the
+// element matrices this library already forms.
 //
 //   body     f_a = rho int N_a a dV          c3d4: rho V/4 g, or rho V/20 (a_a + sum_b a_b) for a nodal field
 //                                            c3d8 / c3d6 / c3d10: rho sum_q w_q |detJ_q| N_a(q) a(q)
 //   thermal  f_a = int B_a^T D (alpha dT m)  m = (1,1,1,0,0,0); D m = (D00 + 2 D01) m, so f_a = c (D00 + 2 D01)
 //                                            alpha dT grad N_a with the volume factor c of the family's K_e
 //   surface  f_a = -int N_a p n dA  or  int N_a t dA   over tri3 (one point) / quad4 (2x2 Gauss on x_xi x x_eta)
-//   stress   sigma = D (B u_e - alpha dT m), von Mises of that tensor
 //
 // Every nodal sum is a gather over the sorted node -> element incidence in ascending order: no atomics, the same bits
 // on every run, zero rows for nodes without elements. All arithmetic fp64.
@@ -16,18 +15,9 @@
 
 namespace fem {
 
-struct LoadD {
-    double d0, d1, g;   // D[0][0], D[0][1], D[3][3] of the reference's isotropic D (`solver/element.py:282-306`)
-};
-
-static inline LoadD load_d(double E, double nu) {
-    const double c = E / ((1.0 + nu) * (1.0 - 2.0 * nu));
-    return LoadD{c * (1.0 - nu), c * nu, c * ((1.0 - 2.0 * nu) / 2.0)};
-}
-
 // (D alpha m)'s normal entry: the thermal load per unit dT and unit gradient
 static inline double thermal_beta(double E, double nu, double alpha) {
-    const LoadD D = load_d(E, nu);
+    const Dmat D = dmat(E, nu);
     return (D.d0 + D.d1 + D.d1) * alpha;
 }
 
@@ -149,8 +139,6 @@ __global__ void __launch_bounds__(256) k_tet4_loads_elem(Tet4LoadArgs A, int64_t
 }
 
 // ---------------------------------------------------------------- isoparametric volume loads (thread per element)
-constexpr int LOAD_MAX_IP = 32;
-
 template <int NPE>
 __global__ void __launch_bounds__(256) k_iso_loads(const double* __restrict__ X, const int64_t* __restrict__ conn,
                                                    int64_t M, const double* __restrict__ Nv,
@@ -158,9 +146,9 @@ __global__ void __launch_bounds__(256) k_iso_loads(const double* __restrict__ X,
                                                    int n_ip, int mode, double rho, const double* __restrict__ accel,
                                                    int amode, double beta, const double* __restrict__ T, int tmode,
                                                    double Tref, double* __restrict__ fe) {
-    __shared__ double dn_s[LOAD_MAX_IP * NPE * 3];
-    __shared__ double nv_s[LOAD_MAX_IP * NPE];
-    __shared__ double w_s[LOAD_MAX_IP];
+    __shared__ double dn_s[ISO_MAX_IP * NPE * 3];
+    __shared__ double nv_s[ISO_MAX_IP * NPE];
+    __shared__ double w_s[ISO_MAX_IP];
     for (int t = threadIdx.x; t < n_ip * NPE * 3; t += blockDim.x) dn_s[t] = dN[t];
     for (int t = threadIdx.x; t < n_ip * NPE; t += blockDim.x) nv_s[t] = Nv[t];
     for (int t = threadIdx.x; t < n_ip; t += blockDim.x) w_s[t] = w[t];
@@ -366,162 +354,6 @@ __global__ void __launch_bounds__(256) k_face_loads(const double* __restrict__ X
     }
 }
 
-// ---------------------------------------------------------------- thermal stress
-// strain (minus alpha dT on the normal entries) -> stress (6) -> von Mises; the arithmetic of stress.hip's
-// point_stress with the thermal strain taken off before D
-template <int NPE>
-__device__ __forceinline__ double point_stress_th(const double g[NPE][3], const double u[NPE][3], const LoadD& D,
-                                                  double eth, double s[6]) {
-    double e[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int a = 0; a < NPE; ++a) {
-        e[0] += g[a][0] * u[a][0];
-        e[1] += g[a][1] * u[a][1];
-        e[2] += g[a][2] * u[a][2];
-        e[3] += g[a][1] * u[a][0] + g[a][0] * u[a][1];
-        e[4] += g[a][2] * u[a][1] + g[a][1] * u[a][2];
-        e[5] += g[a][2] * u[a][0] + g[a][0] * u[a][2];
-    }
-    e[0] -= eth;
-    e[1] -= eth;
-    e[2] -= eth;
-    s[0] = D.d0 * e[0] + D.d1 * e[1] + D.d1 * e[2];
-    s[1] = D.d1 * e[0] + D.d0 * e[1] + D.d1 * e[2];
-    s[2] = D.d1 * e[0] + D.d1 * e[1] + D.d0 * e[2];
-    s[3] = D.g * e[3];
-    s[4] = D.g * e[4];
-    s[5] = D.g * e[5];
-    const double a = s[0] - s[1], b = s[1] - s[2], c = s[2] - s[0];
-    return sqrt((a * a + b * b + c * c + 6.0 * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5])) / 2.0);
-}
-
-// symmetric tensor rows (xx xy xz / xy yy yz / xz yz zz) with Voigt (xx, yy, zz, xy, yz, xz)
-__device__ __forceinline__ void store_tensor_th(double* __restrict__ out, const double s[6]) {
-    out[0] = s[0];
-    out[1] = s[3];
-    out[2] = s[5];
-    out[3] = s[3];
-    out[4] = s[1];
-    out[5] = s[4];
-    out[6] = s[5];
-    out[7] = s[4];
-    out[8] = s[2];
-}
-
-// c3d4: thread per element in 256-element tiles, connectivity in and tensors out through LDS (k_tet4_stress's shape)
-constexpr int TH_TILE = 256;
-
-__global__ void __launch_bounds__(TH_TILE) k_tet4_stress_th(const double* __restrict__ X,
-                                                            const int64_t* __restrict__ conn, int64_t M,
-                                                            const double* __restrict__ U, LoadD D, double alpha,
-                                                            const double* __restrict__ T, int tmode, double Tref,
-                                                            double* __restrict__ sig, double* __restrict__ vm,
-                                                            int64_t* __restrict__ bad) {
-    __shared__ int64_t c_s[TH_TILE * 4];
-    __shared__ double s_s[TH_TILE * 9];
-    const int64_t ntiles = (M + TH_TILE - 1) / TH_TILE;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t e0 = tile * TH_TILE;
-        const int nt = (int)min((int64_t)TH_TILE, M - e0);
-        for (int t = threadIdx.x; t < 4 * nt; t += TH_TILE) c_s[t] = conn[4 * e0 + t];
-        __syncthreads();
-        if ((int)threadIdx.x < nt) {
-            const int64_t e = e0 + threadIdx.x;
-            const int64_t* c = c_s + 4 * threadIdx.x;
-            double g[4][3], u[4][3];
-            const double det = tet4_grads(X, c, g);
-            if (bad && fabs(det) < 1e-12) atomicMin((unsigned long long*)bad, (unsigned long long)e);
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) u[a][k] = U[3 * c[a] + k];
-            double dT;
-            if (tmode == FEM_LOAD_UNIFORM) dT = T[0] - Tref;
-            else if (tmode == FEM_LOAD_ELEMENT) dT = T[e] - Tref;
-            else dT = ((((T[c[0]] - Tref) + (T[c[1]] - Tref)) + (T[c[2]] - Tref)) + (T[c[3]] - Tref)) / 4.0;
-            double s[6];
-            const double v = point_stress_th<4>(g, u, D, alpha * dT, s);
-            store_tensor_th(s_s + 9 * threadIdx.x, s);
-            if (vm) vm[e] = v;
-        }
-        __syncthreads();
-        if (sig)
-            for (int t = threadIdx.x; t < 9 * nt; t += TH_TILE) sig[9 * e0 + t] = s_s[t];
-        __syncthreads();
-    }
-}
-
-// isoparametric: thread per element, all points (k_iso_stress's shape plus the shape values that interpolate dT).
-// layout 0: weighted sums [M,3,3] / [M]; 1: per point [M,n_ip,3,3] / [M,n_ip]
-template <int NPE>
-__global__ void __launch_bounds__(256) k_iso_stress_th(const double* __restrict__ X, const int64_t* __restrict__ conn,
-                                                       int64_t M, const double* __restrict__ U, LoadD D, double alpha,
-                                                       const double* __restrict__ T, int tmode, double Tref,
-                                                       const double* __restrict__ Nv, const double* __restrict__ dN,
-                                                       const double* __restrict__ w, int n_ip, int layout,
-                                                       double* __restrict__ sig, double* __restrict__ vm) {
-    __shared__ double dn_s[LOAD_MAX_IP * NPE * 3];
-    __shared__ double nv_s[LOAD_MAX_IP * NPE];
-    __shared__ double w_s[LOAD_MAX_IP];
-    for (int t = threadIdx.x; t < n_ip * NPE * 3; t += blockDim.x) dn_s[t] = dN[t];
-    for (int t = threadIdx.x; t < n_ip * NPE; t += blockDim.x) nv_s[t] = Nv[t];
-    for (int t = threadIdx.x; t < n_ip; t += blockDim.x) w_s[t] = w ? w[t] : 0.0;
-    __syncthreads();
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (int64_t)gridDim.x * blockDim.x) {
-        double x[NPE][3], u[NPE][3], dTn[NPE];
-#pragma unroll
-        for (int a = 0; a < NPE; ++a) {
-            const int64_t n = conn[(int64_t)NPE * e + a];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                x[a][k] = X[3 * n + k];
-                u[a][k] = U[3 * n + k];
-            }
-            dTn[a] = tmode == FEM_LOAD_NODAL ? T[n] - Tref : 0.0;
-        }
-        const double dTe = tmode == FEM_LOAD_UNIFORM ? T[0] - Tref : (tmode == FEM_LOAD_ELEMENT ? T[e] - Tref : 0.0);
-        double acc[6] = {0, 0, 0, 0, 0, 0}, vacc = 0.0;
-        for (int q = 0; q < n_ip; ++q) {
-            const double* dq = dn_s + q * NPE * 3;
-            double J[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int j = 0; j < NPE; ++j)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) J[3 * i + k] += dq[j * 3 + i] * x[j][k];
-            double Ji[9];
-            inv3(J, Ji);
-            double g[NPE][3];
-#pragma unroll
-            for (int n = 0; n < NPE; ++n)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    g[n][i] = Ji[3 * i] * dq[n * 3] + Ji[3 * i + 1] * dq[n * 3 + 1] + Ji[3 * i + 2] * dq[n * 3 + 2];
-            double dT = dTe;
-            if (tmode == FEM_LOAD_NODAL) {
-#pragma unroll
-                for (int b = 0; b < NPE; ++b) dT += nv_s[q * NPE + b] * dTn[b];
-            }
-            double s[6];
-            const double v = point_stress_th<NPE>(g, u, D, alpha * dT, s);
-            if (layout == 0) {
-#pragma unroll
-                for (int t = 0; t < 6; ++t) acc[t] += w_s[q] * s[t];
-                vacc += w_s[q] * v;
-            } else {
-                const int64_t slot = e * n_ip + q;
-                if (sig) store_tensor_th(sig + 9 * slot, s);
-                if (vm) vm[slot] = v;
-            }
-        }
-        if (layout == 0) {
-            if (sig) store_tensor_th(sig + 9 * e, acc);
-            if (vm) vm[e] = vacc;
-        }
-    }
-}
-
 static bool mode_ok(int mode, bool element_ok) {
     return mode == FEM_LOAD_NONE || mode == FEM_LOAD_UNIFORM || mode == FEM_LOAD_NODAL ||
            (element_ok && mode == FEM_LOAD_ELEMENT);
@@ -589,8 +421,8 @@ int fem_iso_loads(const double* coords, const int64_t* conn, int64_t M, int npe,
         set_error("fem_iso_loads: mode %d (FEM_ISO_SUM, or FEM_ISO_VOLUME for npe 6 at one point)", mode);
         return FEM_EARG;
     }
-    if (n_ip < 1 || n_ip > LOAD_MAX_IP) {
-        set_error("fem_iso_loads: n_ip = %d out of range [1, %d]", n_ip, LOAD_MAX_IP);
+    if (n_ip < 1 || n_ip > ISO_MAX_IP) {
+        set_error("fem_iso_loads: n_ip = %d out of range [1, %d]", n_ip, ISO_MAX_IP);
         return FEM_EARG;
     }
     if (npe != 6 && npe != 8 && npe != 10) {
@@ -631,49 +463,6 @@ int fem_face_loads(const double* coords, const int64_t* faces, int64_t F, int nf
         hipLaunchKernelGGL(k_face_loads<3>, g, b, 0, S(stream), coords, faces, extra, F, p, p_mode, t, t_mode, fv);
     else
         hipLaunchKernelGGL(k_face_loads<4>, g, b, 0, S(stream), coords, faces, extra, F, p, p_mode, t, t_mode, fv);
-    FEM_LAUNCHED();
-    return FEM_OK;
-}
-
-int fem_tet4_stress_thermal(const double* coords, const int64_t* conn, int64_t M, const double* u, double E, double nu,
-                            double alpha, const double* T, int t_mode, double T_ref, double* sig, double* vm,
-                            int64_t* bad_idx, fem_stream_t stream) {
-    if (t_mode == FEM_LOAD_NONE || !mode_ok(t_mode, true) || !T) {
-        set_error("fem_tet4_stress_thermal: t_mode %d invalid or T missing", t_mode);
-        return FEM_EARG;
-    }
-    if (M <= 0) return FEM_OK;
-    hipLaunchKernelGGL(k_tet4_stress_th, dim3(stream_grid(M, 256)), dim3(256), 0, S(stream), coords, conn, M, u,
-                       load_d(E, nu), alpha, T, t_mode, T_ref, sig, vm, bad_idx);
-    FEM_LAUNCHED();
-    return FEM_OK;
-}
-
-int fem_iso_stress_thermal(const double* coords, const int64_t* conn, int64_t M, int npe, const double* u, double E,
-                           double nu, double alpha, const double* T, int t_mode, double T_ref, const double* Nv,
-                           const double* dN, const double* w, int n_ip, int layout, double* sig, double* vm,
-                           fem_stream_t stream) {
-    if (t_mode == FEM_LOAD_NONE || !mode_ok(t_mode, true) || !T) {
-        set_error("fem_iso_stress_thermal: t_mode %d invalid or T missing", t_mode);
-        return FEM_EARG;
-    }
-    if (n_ip < 1 || n_ip > LOAD_MAX_IP || layout < 0 || layout > 1 || (layout == 0 && !w)) {
-        set_error("fem_iso_stress_thermal: n_ip must be in [1, %d], layout in {0,1} (0 needs weights)", LOAD_MAX_IP);
-        return FEM_EARG;
-    }
-    if (npe != 6 && npe != 8) {
-        set_error("fem_iso_stress_thermal: npe %d not supported (6, 8)", npe);
-        return FEM_EBADTYPE;
-    }
-    if (M <= 0) return FEM_OK;
-    const dim3 g(stream_grid(M, 256)), b(256);
-    const LoadD D = load_d(E, nu);
-    if (npe == 6)
-        hipLaunchKernelGGL(k_iso_stress_th<6>, g, b, 0, S(stream), coords, conn, M, u, D, alpha, T, t_mode, T_ref, Nv,
-                           dN, w, n_ip, layout, sig, vm);
-    else
-        hipLaunchKernelGGL(k_iso_stress_th<8>, g, b, 0, S(stream), coords, conn, M, u, D, alpha, T, t_mode, T_ref, Nv,
-                           dN, w, n_ip, layout, sig, vm);
     FEM_LAUNCHED();
     return FEM_OK;
 }

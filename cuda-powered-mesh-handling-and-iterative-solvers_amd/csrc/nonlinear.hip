@@ -18,7 +18,7 @@ namespace fem {
 
 // per-element record in LDS (doubles): what the block formula reads, then the element forces
 constexpr int NL_X = 0;     // [4][3] F g_a (svk) / h_a (neo-Hooke)
-constexpr int NL_GG = 12;   // [10] g_a.g_b, a <= b, at ke_sym_blk(4, a, b)
+constexpr int NL_GG = 12;   // [10] g_a.g_b, a <= b, at sym_blk(4, a, b)
 constexpr int NL_C = 22;    // [10] the d_ik factor: g_a.S g_b (svk) / mu g_a.g_b (neo-Hooke)
 constexpr int NL_FF = 32;   // [6] F F^T (xx, yy, zz, xy, yz, xz), svk only
 constexpr int NL_V = 38;    // V (0 for an element whose outputs are zero)
@@ -27,8 +27,6 @@ constexpr int NL_TAN = 40;  // record length of the tangent part
 constexpr int NL_REC_T = 53;   // tangent part + 12 forces, odd stride
 constexpr int NL_REC_F = 13;   // forces only
 
-__host__ __device__ constexpr int nl_blk(int a, int b) { return a * 4 - a * (a - 1) / 2 + (b - a); }
-
 // entry (i, k) of the upper block (a, b), a <= b, from the element's record. The packed and the full form both come
 // through here with the same arguments (the full form's lower blocks with (a, i) and (b, k) exchanged), and no product
 // is fused into a sum, so the two agree bit for bit and the full matrix is exactly symmetric.
@@ -36,7 +34,7 @@ template <int MAT>
 __device__ __forceinline__ double nl_entry(const double* __restrict__ r, int a, int b, int i, int k, double lam,
                                            double mu) {
 #pragma clang fp contract(off)
-    const int blk = nl_blk(a, b);
+    const int blk = sym_blk(4, a, b);
     const double* xa = r + NL_X + 3 * a;
     const double* xb = r + NL_X + 3 * b;
     const double p = xa[i] * xb[k];
@@ -51,32 +49,8 @@ __device__ __forceinline__ double nl_entry(const double* __restrict__ r, int a, 
     return s * r[NL_V];
 }
 
-// a b - c d with the rounding error of c d carried along (Kahan): within 1.5 ulp of the exact difference, where the
-// plain form loses every digit the two products share
-__device__ __forceinline__ double nl_dop(double a, double b, double c, double d) {
-#pragma clang fp contract(off)
-    const double w = c * d;
-    const double e = fma(-c, d, w);
-    const double f = fma(a, b, -w);
-    return f + e;
-}
-
-// x0 y0 + x1 y1 + x2 y2 with the errors of the products and of the two sums collected and added once
-__device__ __forceinline__ double nl_dot3c(double x0, double y0, double x1, double y1, double x2, double y2) {
-#pragma clang fp contract(off)
-    const double p0 = x0 * y0, p1 = x1 * y1, p2 = x2 * y2;
-    const double e0 = fma(x0, y0, -p0), e1 = fma(x1, y1, -p1), e2 = fma(x2, y2, -p2);
-    const double s = p0 + p1;
-    const double b1 = s - p0;
-    const double t1 = (p0 - (s - b1)) + (p1 - b1);
-    const double s2 = s + p2;
-    const double b2 = s2 - s;
-    const double t2 = (s - (s2 - b2)) + (p2 - b2);
-    return s2 + ((t1 + t2) + ((e0 + e1) + e2));
-}
-
 // One lane: everything of element e that does not depend on the output entry, into the record r and the per-element
-// outputs. det F and the cofactors of F are formed by nl_dop / nl_dot3c: a deformation gradient with entries far above
+// outputs. det F and the cofactors of F are formed by dop / dot3c (element.hpp): a deformation gradient with entries far above
 // its determinant (a sliver mesh carrying a finite strain: F ~ 1e3, J ~ 1) left the plain cofactor expansion 35 x
 // less accurate than the rounding of F itself allows (tests/test_gpu_hard_geometry_nl.py). An inverted element (det F <= 0) or a degenerate reference element gets a zero record, zero stress and
 // energy +inf; no logarithm of a non-positive number is taken and no NaN is stored. Products are not fused into sums
@@ -95,17 +69,12 @@ __device__ __forceinline__ void nl_element(const double* __restrict__ X, const i
     const bool degenerate = !(fabs(det) >= 1e-12);
     if (degenerate) atomicMin((unsigned long long*)bad, (unsigned long long)e);
     const double V = fabs(det) / 6.0;
-    double H[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    double u[4][3], H[3][3];
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const double u0 = U[3 * n[a]], u1 = U[3 * n[a] + 1], u2 = U[3 * n[a] + 2];
+    for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            H[0][j] += u0 * g[a][j];
-            H[1][j] += u1 * g[a][j];
-            H[2][j] += u2 * g[a][j];
-        }
-    }
+        for (int k = 0; k < 3; ++k) u[a][k] = U[3 * n[a] + k];
+    tet4_disp_grad(u, g, H);
     double F[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -113,10 +82,10 @@ __device__ __forceinline__ void nl_element(const double* __restrict__ X, const i
         for (int j = 0; j < 3; ++j) F[i][j] = (i == j ? 1.0 : 0.0) + H[i][j];
     // cofactors of F (Cf[i][j] = cofactor of F[i][j]); det F by the first row
     double Cf[3][3];
-    Cf[0][0] = nl_dop(F[1][1], F[2][2], F[1][2], F[2][1]);
-    Cf[0][1] = nl_dop(F[1][2], F[2][0], F[1][0], F[2][2]);
-    Cf[0][2] = nl_dop(F[1][0], F[2][1], F[1][1], F[2][0]);
-    const double J = nl_dot3c(F[0][0], Cf[0][0], F[0][1], Cf[0][1], F[0][2], Cf[0][2]);
+    Cf[0][0] = dop(F[1][1], F[2][2], F[1][2], F[2][1]);
+    Cf[0][1] = dop(F[1][2], F[2][0], F[1][0], F[2][2]);
+    Cf[0][2] = dop(F[1][0], F[2][1], F[1][1], F[2][0]);
+    const double J = dot3c(F[0][0], Cf[0][0], F[0][1], Cf[0][1], F[0][2], Cf[0][2]);
     const bool ok = !degenerate && J > 0.0;   // false for a NaN as well
     if (detF) detF[e] = (degenerate || J != J) ? 0.0 : J;
     if (!ok) {
@@ -176,7 +145,7 @@ __device__ __forceinline__ void nl_element(const double* __restrict__ X, const i
             for (int a = 0; a < 4; ++a)
 #pragma unroll
                 for (int b = a; b < 4; ++b)
-                    r[NL_C + nl_blk(a, b)] = (g[a][0] * Sg[b][0] + g[a][1] * Sg[b][1]) + g[a][2] * Sg[b][2];
+                    r[NL_C + sym_blk(4, a, b)] = (g[a][0] * Sg[b][0] + g[a][1] * Sg[b][1]) + g[a][2] * Sg[b][2];
 #pragma unroll
             for (int t = 0; t < 6; ++t) r[NL_FF + t] = FFt[t];
             r[NL_COEF] = 0.0;
@@ -201,12 +170,12 @@ __device__ __forceinline__ void nl_element(const double* __restrict__ X, const i
                 for (int i = 0; i < 3; ++i) r[NL_X + 3 * a + i] = Fg[a][i];
         }
     } else {
-        Cf[1][0] = nl_dop(F[0][2], F[2][1], F[0][1], F[2][2]);
-        Cf[1][1] = nl_dop(F[0][0], F[2][2], F[0][2], F[2][0]);
-        Cf[1][2] = nl_dop(F[0][1], F[2][0], F[0][0], F[2][1]);
-        Cf[2][0] = nl_dop(F[0][1], F[1][2], F[0][2], F[1][1]);
-        Cf[2][1] = nl_dop(F[0][2], F[1][0], F[0][0], F[1][2]);
-        Cf[2][2] = nl_dop(F[0][0], F[1][1], F[0][1], F[1][0]);
+        Cf[1][0] = dop(F[0][2], F[2][1], F[0][1], F[2][2]);
+        Cf[1][1] = dop(F[0][0], F[2][2], F[0][2], F[2][0]);
+        Cf[1][2] = dop(F[0][1], F[2][0], F[0][0], F[2][1]);
+        Cf[2][0] = dop(F[0][1], F[1][2], F[0][2], F[1][1]);
+        Cf[2][1] = dop(F[0][2], F[1][0], F[0][0], F[1][2]);
+        Cf[2][2] = dop(F[0][0], F[1][1], F[0][1], F[1][0]);
         const double lnJ = log(J);
         // h_a = F^-T g_a = (cofactor matrix) g_a / J
         double h[4][3];
@@ -257,8 +226,8 @@ __device__ __forceinline__ void nl_element(const double* __restrict__ X, const i
 #pragma unroll
             for (int b = a; b < 4; ++b) {
                 const double gg = (g[a][0] * g[b][0] + g[a][1] * g[b][1]) + g[a][2] * g[b][2];
-                r[NL_GG + nl_blk(a, b)] = gg;
-                if (MAT != FEM_MAT_SVK) r[NL_C + nl_blk(a, b)] = mu * gg;
+                r[NL_GG + sym_blk(4, a, b)] = gg;
+                if (MAT != FEM_MAT_SVK) r[NL_C + sym_blk(4, a, b)] = mu * gg;
             }
         r[NL_V] = V;
     }
@@ -269,10 +238,10 @@ __device__ __forceinline__ void nl_element(const double* __restrict__ X, const i
     }
 }
 
-// 64 elements per 256-thread block (the shape of k_tet4_ke): 64 lanes form the records into LDS, then all 256 threads
-// write the block's contiguous tangent values and element forces coalesced. TAN = false (Kt == NULL, the line
-// search's trial evaluations) has no tangent record and no tangent store. PACKED: fem_iso_ke_sym's layout for npe = 4
-// (90 doubles per element), else the full [12, 12].
+// 64 elements per 256-thread block: 64 lanes form the records into LDS, then all 256 threads write them out through
+// the c3d4 tangent shell of element.hpp. TAN = false (Kt == NULL, the line search's trial evaluations) has no tangent
+// record and no tangent store. PACKED: fem_iso_ke_sym's layout for npe = 4 (90 doubles per element), else the full
+// [12, 12].
 template <int MAT, bool TAN, bool PACKED>
 __global__ void __launch_bounds__(256) k_tet4_nl(const double* __restrict__ X, const int64_t* __restrict__ conn,
                                                  int64_t M, const double* __restrict__ U, double E, double nu,
@@ -292,44 +261,11 @@ __global__ void __launch_bounds__(256) k_tet4_nl(const double* __restrict__ X, c
     }
     __syncthreads();
     const int nel = (int)min((int64_t)64, M - e0);
-    if (TAN) {
-        constexpr int PS = PACKED ? 90 : 144;
-        const int nval = nel * PS;
-        double* out = Kt + e0 * PS;
-        for (int t = threadIdx.x; t < nval; t += 256) {
-            const int le = t / PS;
-            const int q = t - le * PS;
-            int a, b, i, k;
-            if (PACKED) {
-                const int blk = q / 9, rc = q - 9 * (q / 9);
-                a = blk < 4 ? 0 : (blk < 7 ? 1 : (blk < 9 ? 2 : 3));
-                b = blk - (a * 4 - a * (a - 1) / 2) + a;
-                i = rc / 3;
-                k = rc - 3 * i;
-            } else {
-                const int row = q / 12, col = q - 12 * (q / 12);
-                a = row / 3;
-                i = row - 3 * a;
-                b = col / 3;
-                k = col - 3 * b;
-                if (a > b) {   // a lower block: the transpose of its upper one
-                    const int ta = a, ti = i;
-                    a = b;
-                    b = ta;
-                    i = k;
-                    k = ti;
-                }
-            }
-            out[t] = nl_entry<MAT>(rec_s + le * REC, a, b, i, k, L.lam, L.mu);
-        }
-    }
-    if (fe) {
-        double* out = fe + e0 * 12;
-        for (int t = threadIdx.x; t < nel * 12; t += 256) {
-            const int le = t / 12;
-            out[t] = rec_s[le * REC + FE0 + (t - 12 * le)];
-        }
-    }
+    if (TAN)
+        tet4_tangent_store<REC, PACKED>(rec_s, e0, nel, Kt, [&](const double* r, int a, int b, int i, int k) {
+            return nl_entry<MAT>(r, a, b, i, k, L.lam, L.mu);
+        });
+    if (fe) tet4_force_store<REC, FE0>(rec_s, e0, nel, fe);
 }
 
 // one thread per node dof: the node's incidence list in ascending (element, local) order (k_ebe_apply's order), so

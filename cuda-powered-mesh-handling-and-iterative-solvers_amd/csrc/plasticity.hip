@@ -24,7 +24,7 @@ namespace fem {
 // per-element record in LDS (doubles): what the block formula reads, then the element forces
 constexpr int J2_G = 0;      // [4][3] g_a
 constexpr int J2_NG = 12;    // [4][3] n g_a (0 for an elastic element)
-constexpr int J2_GG = 24;    // [10] g_a.g_b, a <= b, at j2_blk(a, b)
+constexpr int J2_GG = 24;    // [10] g_a.g_b, a <= b, at sym_blk(4, a, b)
 constexpr int J2_CL = 34;    // kappa - 2 mu beta / 3
 constexpr int J2_CM = 35;    // mu beta
 constexpr int J2_CN = 36;    // the n(x)n factor (0 for an elastic element)
@@ -32,8 +32,6 @@ constexpr int J2_V = 37;     // V (0 for an element whose outputs are zero)
 constexpr int J2_TAN = 38;   // record length of the tangent part
 constexpr int J2_REC_T = 51;   // tangent part + 12 forces, padded to an odd stride
 constexpr int J2_REC_F = 13;   // forces only
-
-__host__ __device__ constexpr int j2_blk(int a, int b) { return a * 4 - a * (a - 1) / 2 + (b - a); }
 
 // entry (i, k) of the upper block (a, b), a <= b, from the element's record. The packed and the full form both come
 // through here with the same arguments (the full form's lower blocks with (a, i) and (b, k) exchanged), and no product
@@ -46,7 +44,7 @@ __device__ __forceinline__ double j2_entry(const double* __restrict__ r, int a, 
     const double q = gb[i] * ga[k];
     const double m = r[J2_NG + 3 * a + i] * r[J2_NG + 3 * b + k];
     double s = r[J2_CL] * p + r[J2_CM] * q;
-    if (i == k) s = s + r[J2_CM] * r[J2_GG + j2_blk(a, b)];
+    if (i == k) s = s + r[J2_CM] * r[J2_GG + sym_blk(4, a, b)];
     s = s - r[J2_CN] * m;
     return s * r[J2_V];
 }
@@ -94,17 +92,12 @@ __device__ __forceinline__ void j2_element(const double* __restrict__ X, const i
         return;
     }
     const double V = fabs(det) / 6.0;
-    double Hm[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    double u[4][3], Hm[3][3];
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const double u0 = U[3 * nd[a]], u1 = U[3 * nd[a] + 1], u2 = U[3 * nd[a] + 2];
+    for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            Hm[0][j] += u0 * g[a][j];
-            Hm[1][j] += u1 * g[a][j];
-            Hm[2][j] += u2 * g[a][j];
-        }
-    }
+        for (int k = 0; k < 3; ++k) u[a][k] = U[3 * nd[a] + k];
+    tet4_disp_grad(u, g, Hm);
     const double tr = (Hm[0][0] + Hm[1][1]) + Hm[2][2];
     const double tm = tr / 3.0;
     // deviatoric strain minus the committed plastic strain, then the trial stress deviator
@@ -160,7 +153,7 @@ __device__ __forceinline__ void j2_element(const double* __restrict__ X, const i
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b = a; b < 4; ++b)
-                r[J2_GG + j2_blk(a, b)] = (g[a][0] * g[b][0] + g[a][1] * g[b][1]) + g[a][2] * g[b][2];
+                r[J2_GG + sym_blk(4, a, b)] = (g[a][0] * g[b][0] + g[a][1] * g[b][1]) + g[a][2] * g[b][2];
         r[J2_CL] = kappa - 2.0 * mu * beta / 3.0;
         r[J2_CM] = mu * beta;
         r[J2_CN] = cn;
@@ -190,10 +183,10 @@ __device__ __forceinline__ void j2_element(const double* __restrict__ X, const i
     if (plastic) plastic[e] = yields ? 1 : 0;
 }
 
-// 64 elements per 256-thread block (the shape of k_tet4_nl): 64 lanes form the records into LDS, then all 256 threads
-// write the block's contiguous tangent values and element forces coalesced. TAN = false (Kt == NULL, the line
-// search's trial evaluations) has no tangent record and no tangent store. PACKED: fem_iso_ke_sym's layout for npe = 4
-// (90 doubles per element), else the full [12, 12].
+// 64 elements per 256-thread block: 64 lanes form the records into LDS, then all 256 threads write them out through
+// the c3d4 tangent shell of element.hpp. TAN = false (Kt == NULL, the line search's trial evaluations) has no tangent
+// record and no tangent store. PACKED: fem_iso_ke_sym's layout for npe = 4 (90 doubles per element), else the full
+// [12, 12].
 template <bool TAN, bool PACKED>
 __global__ void __launch_bounds__(256) k_tet4_j2(const double* __restrict__ X, const int64_t* __restrict__ conn,
                                                  int64_t M, const double* __restrict__ U, double kappa, double mu,
@@ -214,44 +207,8 @@ __global__ void __launch_bounds__(256) k_tet4_j2(const double* __restrict__ X, c
     }
     __syncthreads();
     const int nel = (int)min((int64_t)64, M - e0);
-    if (TAN) {
-        constexpr int PS = PACKED ? 90 : 144;
-        const int nval = nel * PS;
-        double* out = Kt + e0 * PS;
-        for (int t = threadIdx.x; t < nval; t += 256) {
-            const int le = t / PS;
-            const int q = t - le * PS;
-            int a, b, i, k;
-            if (PACKED) {
-                const int blk = q / 9, rc = q - 9 * (q / 9);
-                a = blk < 4 ? 0 : (blk < 7 ? 1 : (blk < 9 ? 2 : 3));
-                b = blk - (a * 4 - a * (a - 1) / 2) + a;
-                i = rc / 3;
-                k = rc - 3 * i;
-            } else {
-                const int row = q / 12, col = q - 12 * (q / 12);
-                a = row / 3;
-                i = row - 3 * a;
-                b = col / 3;
-                k = col - 3 * b;
-                if (a > b) {   // a lower block: the transpose of its upper one
-                    const int ta = a, ti = i;
-                    a = b;
-                    b = ta;
-                    i = k;
-                    k = ti;
-                }
-            }
-            out[t] = j2_entry(rec_s + le * REC, a, b, i, k);
-        }
-    }
-    if (fe) {
-        double* out = fe + e0 * 12;
-        for (int t = threadIdx.x; t < nel * 12; t += 256) {
-            const int le = t / 12;
-            out[t] = rec_s[le * REC + FE0 + (t - 12 * le)];
-        }
-    }
+    if (TAN) tet4_tangent_store<REC, PACKED>(rec_s, e0, nel, Kt, j2_entry);
+    if (fe) tet4_force_store<REC, FE0>(rec_s, e0, nel, fe);
 }
 
 }  // namespace fem

@@ -6,59 +6,14 @@
 // `compute_c3d4_element_stress` (`:905-937`, closed-form P1 gradients); the isoparametric path covers
 // `compute_c3d8_element_stress` (`:1696-1752`), `compute_c3d6_element_stress` (`:2570-2629`) and
 // `compute_c3d10_element_stress` (`:1127-1189`) from host-evaluated natural derivative tables, returning either
-// the weight-summed tensor / von Mises (single=True) or one per point.
+// the weight-summed tensor / von Mises (single=True) or one per point. The thermal entry points (no
+// reference function) are the same kernels with sigma = D (B u_e - alpha dT m), m = (1,1,1,0,0,0).
 //
 // Bandwidth-bound: per element the connectivity, npe coordinates and npe displacements are read (gathers of
 // 24 B rows) and 10 doubles per output point are written; no B matrix is materialised.
 #include "element.hpp"
 
 namespace fem {
-
-struct Dmat {
-    double d0, d1, g;   // D[0][0] = c(1-nu), D[0][1] = c nu, D[3][3] = c (1-2nu)/2
-};
-
-__host__ __device__ inline Dmat dmat(double E, double nu) {
-    const double c = E / ((1.0 + nu) * (1.0 - 2.0 * nu));
-    return Dmat{c * (1.0 - nu), c * nu, c * ((1.0 - 2.0 * nu) / 2.0)};
-}
-
-// strain from gradients g[a][k] and displacements u[a][k] -> stress (6) -> von Mises
-template <int NPE>
-__device__ __forceinline__ double point_stress(const double g[NPE][3], const double u[NPE][3], const Dmat& D,
-                                               double s[6]) {
-    double e[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int a = 0; a < NPE; ++a) {
-        e[0] += g[a][0] * u[a][0];
-        e[1] += g[a][1] * u[a][1];
-        e[2] += g[a][2] * u[a][2];
-        e[3] += g[a][1] * u[a][0] + g[a][0] * u[a][1];
-        e[4] += g[a][2] * u[a][1] + g[a][1] * u[a][2];
-        e[5] += g[a][2] * u[a][0] + g[a][0] * u[a][2];
-    }
-    s[0] = D.d0 * e[0] + D.d1 * e[1] + D.d1 * e[2];
-    s[1] = D.d1 * e[0] + D.d0 * e[1] + D.d1 * e[2];
-    s[2] = D.d1 * e[0] + D.d1 * e[1] + D.d0 * e[2];
-    s[3] = D.g * e[3];
-    s[4] = D.g * e[4];
-    s[5] = D.g * e[5];
-    const double a = s[0] - s[1], b = s[1] - s[2], c = s[2] - s[0];
-    return sqrt((a * a + b * b + c * c + 6.0 * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5])) / 2.0);
-}
-
-// symmetric tensor rows (xx xy xz / xy yy yz / xz yz zz) with Voigt (xx, yy, zz, xy, yz, xz)
-__device__ __forceinline__ void store_tensor(double* __restrict__ out, const double s[6]) {
-    out[0] = s[0];
-    out[1] = s[3];
-    out[2] = s[5];
-    out[3] = s[3];
-    out[4] = s[1];
-    out[5] = s[4];
-    out[6] = s[5];
-    out[7] = s[4];
-    out[8] = s[2];
-}
 
 template <int NPE>
 __device__ __forceinline__ void load_element(const double* __restrict__ X, const double* __restrict__ U,
@@ -74,6 +29,17 @@ __device__ __forceinline__ void load_element(const double* __restrict__ X, const
     }
 }
 
+// The thermal strain alpha dT (fem_*_stress_thermal): T is [1], [N] or [M] by tmode (FEM_LOAD_UNIFORM /
+// NODAL / ELEMENT), Nv [n_ip][NPE] the shape values that interpolate a nodal dT to the points (isoparametric only).
+// The kernels' TH = false instantiations read none of it.
+struct ThermalArgs {
+    double alpha;
+    const double* T;
+    int tmode;
+    double Tref;
+    const double* Nv;
+};
+
 // c3d4: one point, thread per element, 256-element tiles: the tile's connectivity is loaded coalesced through
 // LDS and its [256,3,3] tensor block (18 KB, contiguous in the output) is staged in LDS and written coalesced
 // (a thread-per-element store of 9 doubles would stride the wave's stores by 72 B).
@@ -83,10 +49,11 @@ __device__ __forceinline__ void write_tile(double* __restrict__ dst, const doubl
     for (int t = threadIdx.x; t < nval; t += ST_TILE) dst[t] = lds[t];
 }
 
+template <bool TH>
 __global__ void __launch_bounds__(ST_TILE) k_tet4_stress(const double* __restrict__ X, const int64_t* __restrict__ conn,
                                                          int64_t M, const double* __restrict__ U, Dmat D,
                                                          double* __restrict__ sig, double* __restrict__ vm,
-                                                         int64_t* __restrict__ bad) {
+                                                         int64_t* __restrict__ bad, ThermalArgs th) {
     __shared__ int64_t c_s[ST_TILE * 4];
     __shared__ double s_s[ST_TILE * 9];
     const int64_t ntiles = (M + ST_TILE - 1) / ST_TILE;
@@ -106,8 +73,16 @@ __global__ void __launch_bounds__(ST_TILE) k_tet4_stress(const double* __restric
             for (int a = 0; a < 4; ++a)
 #pragma unroll
                 for (int k = 0; k < 3; ++k) u[a][k] = U[3 * c[a] + k];
+            double dT = 0.0;
+            if constexpr (TH) {
+                const double* T = th.T;
+                const double Tref = th.Tref;
+                if (th.tmode == FEM_LOAD_UNIFORM) dT = T[0] - Tref;
+                else if (th.tmode == FEM_LOAD_ELEMENT) dT = T[e] - Tref;
+                else dT = ((((T[c[0]] - Tref) + (T[c[1]] - Tref)) + (T[c[2]] - Tref)) + (T[c[3]] - Tref)) / 4.0;
+            }
             double s[6];
-            const double v = point_stress<4>(g, u, D, s);
+            const double v = point_stress<4, TH>(g, u, D, th.alpha * dT, s);
             store_tensor(s_s + 9 * threadIdx.x, s);
             if (vm) vm[e] = v;
         }
@@ -117,25 +92,44 @@ __global__ void __launch_bounds__(ST_TILE) k_tet4_stress(const double* __restric
     }
 }
 
-// isoparametric: thread per element, all points; dN [n_ip][NPE][3] and w [n_ip] staged in LDS.
+// isoparametric: thread per element, all points; dN [n_ip][NPE][3] and w [n_ip] (TH: and Nv) staged in LDS.
 // layout 0: single (weighted sums) [M,3,3] / [M]; 1: point-minor [M,n_ip,3,3] / [M,n_ip];
-// 2: point-major [n_ip,M,3,3] / [n_ip,M] (the c3d10 stack, `:1183-1186`)
-constexpr int STRESS_MAX_IP = 32;
-
-template <int NPE>
+// 2: point-major [n_ip,M,3,3] / [n_ip,M] (the c3d10 stack, `:1183-1186`; not with TH)
+template <int NPE, bool TH>
 __global__ void __launch_bounds__(256) k_iso_stress(const double* __restrict__ X, const int64_t* __restrict__ conn,
                                                     int64_t M, const double* __restrict__ U, Dmat D,
                                                     const double* __restrict__ dN, const double* __restrict__ w,
                                                     int n_ip, int layout, double* __restrict__ sig,
-                                                    double* __restrict__ vm) {
-    __shared__ double dn_s[STRESS_MAX_IP * NPE * 3];
-    __shared__ double w_s[STRESS_MAX_IP];
+                                                    double* __restrict__ vm, ThermalArgs th) {
+    __shared__ double dn_s[ISO_MAX_IP * NPE * 3];
+    __shared__ double nv_s[TH ? ISO_MAX_IP * NPE : 1];
+    __shared__ double w_s[ISO_MAX_IP];
     for (int t = threadIdx.x; t < n_ip * NPE * 3; t += blockDim.x) dn_s[t] = dN[t];
+    if constexpr (TH)
+        for (int t = threadIdx.x; t < n_ip * NPE; t += blockDim.x) nv_s[t] = th.Nv[t];
     for (int t = threadIdx.x; t < n_ip; t += blockDim.x) w_s[t] = w ? w[t] : 0.0;
     __syncthreads();
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (int64_t)gridDim.x * blockDim.x) {
-        double x[NPE][3], u[NPE][3];
-        load_element<NPE>(X, U, conn + (int64_t)NPE * e, x, u);
+        double x[NPE][3], u[NPE][3], dTn[TH ? NPE : 1], dTe = 0.0;
+        // TH: the node ids also index T, so x, u and the nodal dT come from one gather. The two gathers are not
+        // interchangeable: after either one the compiler contracts point_stress's two-product sums differently, and
+        // each instantiation's last bits are pinned by what it has always returned.
+        if constexpr (TH) {
+#pragma unroll
+            for (int a = 0; a < NPE; ++a) {
+                const int64_t n = conn[(int64_t)NPE * e + a];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    x[a][k] = X[3 * n + k];
+                    u[a][k] = U[3 * n + k];
+                }
+                dTn[a] = th.tmode == FEM_LOAD_NODAL ? th.T[n] - th.Tref : 0.0;
+            }
+            dTe = th.tmode == FEM_LOAD_UNIFORM ? th.T[0] - th.Tref
+                                               : (th.tmode == FEM_LOAD_ELEMENT ? th.T[e] - th.Tref : 0.0);
+        } else {
+            load_element<NPE>(X, U, conn + (int64_t)NPE * e, x, u);
+        }
         double acc[6] = {0, 0, 0, 0, 0, 0}, vacc = 0.0;
         for (int q = 0; q < n_ip; ++q) {
             const double* dq = dn_s + q * NPE * 3;
@@ -154,14 +148,21 @@ __global__ void __launch_bounds__(256) k_iso_stress(const double* __restrict__ X
 #pragma unroll
                 for (int i = 0; i < 3; ++i)
                     g[n][i] = Ji[3 * i] * dq[n * 3] + Ji[3 * i + 1] * dq[n * 3 + 1] + Ji[3 * i + 2] * dq[n * 3 + 2];
+            double dT = dTe;
+            if constexpr (TH) {
+                if (th.tmode == FEM_LOAD_NODAL) {
+#pragma unroll
+                    for (int b = 0; b < NPE; ++b) dT += nv_s[q * NPE + b] * dTn[b];
+                }
+            }
             double s[6];
-            const double v = point_stress<NPE>(g, u, D, s);
+            const double v = point_stress<NPE, TH>(g, u, D, th.alpha * dT, s);
             if (layout == 0) {
 #pragma unroll
                 for (int t = 0; t < 6; ++t) acc[t] += w_s[q] * s[t];
                 vacc += w_s[q] * v;
             } else {
-                const int64_t slot = layout == 1 ? e * n_ip + q : (int64_t)q * M + e;
+                const int64_t slot = (TH || layout == 1) ? e * n_ip + q : (int64_t)q * M + e;
                 if (sig) store_tensor(sig + 9 * slot, s);
                 if (vm) vm[slot] = v;
             }
@@ -244,13 +245,35 @@ __global__ void k_von_mises(const double* __restrict__ t, int64_t M, double* __r
 
 using namespace fem;
 
+static bool thermal_mode_ok(int t_mode) {
+    return t_mode == FEM_LOAD_UNIFORM || t_mode == FEM_LOAD_NODAL || t_mode == FEM_LOAD_ELEMENT;
+}
+
+#define FEM_ISO_STRESS(NPE_, TH_)                                                                                     \
+    hipLaunchKernelGGL((k_iso_stress<NPE_, TH_>), g, b, 0, S(stream), coords, conn, M, u, D, dN, w, n_ip, layout, sig, \
+                       vm, th)
+
 extern "C" {
 
 int fem_tet4_stress(const double* coords, const int64_t* conn, int64_t M, const double* u, double E, double nu,
                     double* sig, double* vm, int64_t* bad_idx, fem_stream_t stream) {
     if (M <= 0) return FEM_OK;
-    hipLaunchKernelGGL(k_tet4_stress, dim3(stream_grid(M, 256)), dim3(256), 0, S(stream), coords, conn, M, u,
-                       dmat(E, nu), sig, vm, bad_idx);
+    hipLaunchKernelGGL(k_tet4_stress<false>, dim3(stream_grid(M, 256)), dim3(256), 0, S(stream), coords, conn, M, u,
+                       dmat(E, nu), sig, vm, bad_idx, ThermalArgs{});
+    FEM_LAUNCHED();
+    return FEM_OK;
+}
+
+int fem_tet4_stress_thermal(const double* coords, const int64_t* conn, int64_t M, const double* u, double E, double nu,
+                            double alpha, const double* T, int t_mode, double T_ref, double* sig, double* vm,
+                            int64_t* bad_idx, fem_stream_t stream) {
+    if (!thermal_mode_ok(t_mode) || !T) {
+        set_error("fem_tet4_stress_thermal: t_mode %d invalid or T missing", t_mode);
+        return FEM_EARG;
+    }
+    if (M <= 0) return FEM_OK;
+    hipLaunchKernelGGL(k_tet4_stress<true>, dim3(stream_grid(M, 256)), dim3(256), 0, S(stream), coords, conn, M, u,
+                       dmat(E, nu), sig, vm, bad_idx, ThermalArgs{alpha, T, t_mode, T_ref, nullptr});
     FEM_LAUNCHED();
     return FEM_OK;
 }
@@ -258,17 +281,18 @@ int fem_tet4_stress(const double* coords, const int64_t* conn, int64_t M, const 
 int fem_iso_stress(const double* coords, const int64_t* conn, int64_t M, int npe, const double* u, double E, double nu,
                    const double* dN, const double* w, int n_ip, int layout, double* sig, double* vm,
                    fem_stream_t stream) {
-    if (n_ip < 1 || n_ip > STRESS_MAX_IP || layout < 0 || layout > 2 || (layout == 0 && !w)) {
-        set_error("fem_iso_stress: n_ip must be in [1, %d], layout in {0,1,2} (0 needs weights)", STRESS_MAX_IP);
+    if (n_ip < 1 || n_ip > ISO_MAX_IP || layout < 0 || layout > 2 || (layout == 0 && !w)) {
+        set_error("fem_iso_stress: n_ip must be in [1, %d], layout in {0,1,2} (0 needs weights)", ISO_MAX_IP);
         return FEM_EARG;
     }
     if (M <= 0) return FEM_OK;
     const dim3 g(stream_grid(M, 256)), b(256);
     const Dmat D = dmat(E, nu);
+    const ThermalArgs th{};
     switch (npe) {
-        case 6: hipLaunchKernelGGL(k_iso_stress<6>, g, b, 0, S(stream), coords, conn, M, u, D, dN, w, n_ip, layout, sig, vm); break;
-        case 8: hipLaunchKernelGGL(k_iso_stress<8>, g, b, 0, S(stream), coords, conn, M, u, D, dN, w, n_ip, layout, sig, vm); break;
-        case 10: hipLaunchKernelGGL(k_iso_stress<10>, g, b, 0, S(stream), coords, conn, M, u, D, dN, w, n_ip, layout, sig, vm); break;
+        case 6: FEM_ISO_STRESS(6, false); break;
+        case 8: FEM_ISO_STRESS(8, false); break;
+        case 10: FEM_ISO_STRESS(10, false); break;
         default:
             set_error("fem_iso_stress: npe %d not supported (6, 8, 10)", npe);
             return FEM_EBADTYPE;
@@ -276,6 +300,33 @@ int fem_iso_stress(const double* coords, const int64_t* conn, int64_t M, int npe
     FEM_LAUNCHED();
     return FEM_OK;
 }
+
+int fem_iso_stress_thermal(const double* coords, const int64_t* conn, int64_t M, int npe, const double* u, double E,
+                           double nu, double alpha, const double* T, int t_mode, double T_ref, const double* Nv,
+                           const double* dN, const double* w, int n_ip, int layout, double* sig, double* vm,
+                           fem_stream_t stream) {
+    if (!thermal_mode_ok(t_mode) || !T) {
+        set_error("fem_iso_stress_thermal: t_mode %d invalid or T missing", t_mode);
+        return FEM_EARG;
+    }
+    if (n_ip < 1 || n_ip > ISO_MAX_IP || layout < 0 || layout > 1 || (layout == 0 && !w)) {
+        set_error("fem_iso_stress_thermal: n_ip must be in [1, %d], layout in {0,1} (0 needs weights)", ISO_MAX_IP);
+        return FEM_EARG;
+    }
+    if (npe != 6 && npe != 8) {
+        set_error("fem_iso_stress_thermal: npe %d not supported (6, 8)", npe);
+        return FEM_EBADTYPE;
+    }
+    if (M <= 0) return FEM_OK;
+    const dim3 g(stream_grid(M, 256)), b(256);
+    const Dmat D = dmat(E, nu);
+    const ThermalArgs th{alpha, T, t_mode, T_ref, Nv};
+    if (npe == 6) FEM_ISO_STRESS(6, true);
+    else FEM_ISO_STRESS(8, true);
+    FEM_LAUNCHED();
+    return FEM_OK;
+}
+#undef FEM_ISO_STRESS
 
 int fem_voigt_to_tensor(const double* voigt, int64_t M, double* tensor, fem_stream_t stream) {
     if (M <= 0) return FEM_OK;

@@ -156,13 +156,12 @@ __global__ void __launch_bounds__(256) k_tet4_unit_energy(const double* __restri
         if (!(fabs(det) >= 1e-12)) {
             atomicMin((unsigned long long*)bad, (unsigned long long)e);
         } else {
-            double H[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+            double u[4][3], H[3][3];
 #pragma unroll
             for (int a = 0; a < 4; ++a)
 #pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) H[i][j] += r[6 * a + 3 + i] * g[a][j];
+                for (int k = 0; k < 3; ++k) u[a][k] = r[6 * a + 3 + k];
+            tet4_disp_grad(u, g, H);
             const double exy = 0.5 * (H[0][1] + H[1][0]), eyz = 0.5 * (H[1][2] + H[2][1]),
                          exz = 0.5 * (H[0][2] + H[2][0]);
             const double tr = (H[0][0] + H[1][1]) + H[2][2];

@@ -152,7 +152,7 @@ def test_tet4_hyperelastic(gpu, case, material):
     cancel by 1e8: det F and the svk Cauchy stress were off by 3.2e-08 and the neo-Hooke tangent by 1.8e-08, ratios 38
     and 20 to a calibration form (torch.det / torch.linalg.inv, pivoted) at 8e-10, which is what the rounding of F
     leaves. The kernel now forms each 2 x 2 cofactor as a Kahan difference of products and det F as a compensated
-    3-term dot (nl_dop, nl_dot3c, csrc/nonlinear.hip), and compute_c3d4_deformation_gradient returns the kernel's
+    3-term dot (dop, dot3c, csrc/element.hpp), and compute_c3d4_deformation_gradient returns the kernel's
     det F where it had its own plain expansion in torch."""
     el, _ = _mods()
     c, t = X.tet4_case(case)
