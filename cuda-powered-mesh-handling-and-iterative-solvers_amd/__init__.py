@@ -10,4 +10,16 @@ PKG_DIR = _os.path.dirname(_os.path.abspath(__file__))
 
 from . import mesh  # noqa: E402,F401  (pure torch, no GPU needed)
 
-__all__ = ["mesh", "PKG_DIR"]
+# the multigrid interface, resolved on first use (the submodules load the HIP library's binding)
+_LAZY = {"c3d4_to_c3d10": "topology", "refine_c3d4": "topology", "MeshHierarchy": "topology",
+         "Multigrid": "system", "multigrid_pcg_solver": "solver"}
+
+
+def __getattr__(name):
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+__all__ = ["mesh", "PKG_DIR", *_LAZY]

@@ -211,6 +211,18 @@ SIGNATURES = {
     "fem_pcg2_solve": (_I, [_P, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_D)]),
     "fem_pcg2_scalars": (_I, [_P, ctypes.POINTER(_D)]),
     "fem_pcg2_destroy": (None, [_P]),
+    "fem_refine_edge_slots": (_I, [_P, _L, _P, _L, _P, _P, _P]),
+    "fem_refine_emit": (_I, [_P, _L, _L, _P, _P, _P, _P]),
+    "fem_refine_nodes": (_I, [_P, _L, _P, _L, _P, _P, _P, _P]),
+    "fem_mg_restrict": (_I, [_L, _L, _I, _P, _P, _P, _P, _P, _P]),
+    "fem_mg_prolong": (_I, [_L, _L, _I, _P, _P, _P, _P, _P]),
+    "fem_mg_create": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P, _P, ctypes.POINTER(_P)]),
+    "fem_mg_apply": (_I, [_P, _P, _P]),
+    "fem_mg_sweep": (_I, [_P, _I]),
+    "fem_mg_solve": (_I, [_P, _P, _P, _D, _I, _I, _P, _L, ctypes.POINTER(_I), ctypes.POINTER(_I),
+                          ctypes.POINTER(_D)]),
+    "fem_mg_scalars": (_I, [_P, ctypes.POINTER(_D)]),
+    "fem_mg_destroy": (None, [_P]),
     "fem_spmm_km": (_I, [_L, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "fem_modal_work_len": (_L, []),
     "fem_modal_gram": (_I, [_L, _I, _I, ctypes.POINTER(_P), _P, _P, _P]),

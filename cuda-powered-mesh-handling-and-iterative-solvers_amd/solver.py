@@ -326,7 +326,7 @@ def _static_with_shells(coords, force, fixed, c3d4, c3d6, c3d8, s3, s4, material
 # ============================================================================ fused mesh -> solution pipeline
 def solve_tet4(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, tol=1e-8, max_iter=10000, device="cuda:0",
                rtol=None, reorder=None, operator="assembled", preconditioner="jacobi", n_aggregates=None,
-               modulus_scale=None):
+               modulus_scale=None, hierarchy=None, mg_degree=2):
     """Assembly + Jacobi-PCG straight from the mesh (the benchmark pipeline; no element matrices stored):
     c3d4 Poisson (dpn 1, kappa = E) or elasticity (dpn 3), Dirichlet zero on `fixed` nodes via zeros in the
     exact Jacobi M_inv, reference PCG semantics (absolute tol on sqrt(r.z); `rtol` scales it by sqrt(r0.z0)).
@@ -337,11 +337,23 @@ def solve_tet4(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, tol=1e
     measured with the two-level z).
     modulus_scale: a float64 device tensor [M] -- element e has the stiffness modulus_scale[e] K_e(E, nu) (a
     heterogeneous Young's modulus, or conductivity for kind="poisson"; operator="assembled" only).
+    preconditioner="multigrid" (operator="assembled" only): a V(mg_degree, mg_degree) cycle over `hierarchy`, a
+    topology.MeshHierarchy whose finest level is this mesh (coords / elements must be `hierarchy.fine`); sqrt(r.z) is
+    measured with the multigrid z, the system.Multigrid comes back in `res.multigrid`, the SellMatrix is its finest one.
+    `device` must be the hierarchy's device. The Multigrid holds every level's matrix and the device context until
+    `res.multigrid.close()` (or until the result is dropped); keep it to solve further right-hand sides with
+    `res.multigrid.pcg`.
+    The hierarchy chose its numbering (no `reorder`), the coarse levels have a constant material (no `modulus_scale`).
     Returns (u [N, dpn], PcgResult, SellMatrix)."""
     if modulus_scale is not None and operator == "matfree":
         raise ValueError("modulus_scale needs operator='assembled': the matrix-free operator has no per-element scale")
-    if preconditioner not in ("jacobi", "two-level"):
-        raise ValueError(f"unknown preconditioner {preconditioner!r} (supported: 'jacobi', 'two-level')")
+    if preconditioner not in ("jacobi", "two-level", "multigrid"):
+        raise ValueError(f"unknown preconditioner {preconditioner!r} (supported: 'jacobi', 'two-level', 'multigrid')")
+    if preconditioner == "multigrid":
+        return _solve_tet4_multigrid(coords, elements, f, fixed, kind, E, nu, tol, max_iter, device, rtol, reorder,
+                                     operator, modulus_scale, hierarchy, mg_degree)
+    if hierarchy is not None:
+        raise ValueError("hierarchy= needs preconditioner='multigrid'")
     if preconditioner == "two-level" and (kind != "elastic" or operator != "assembled"):
         raise ValueError("preconditioner='two-level' needs kind='elastic' and operator='assembled' "
                          f"(got kind={kind!r}, operator={operator!r})")
@@ -387,6 +399,86 @@ def solve_tet4(coords, elements, f, fixed, kind="poisson", E=1.0, nu=0.0, tol=1e
     if inv is not None:
         u = u[inv]
     return u, res, A
+
+
+def _solve_tet4_multigrid(coords, elements, f, fixed, kind, E, nu, tol, max_iter, device, rtol, reorder, operator,
+                          modulus_scale, hierarchy, mg_degree):
+    """solve_tet4's preconditioner="multigrid" route."""
+    if hierarchy is None:
+        raise ValueError("preconditioner='multigrid' needs hierarchy= (topology.refine_c3d4 of the coarse mesh)")
+    if operator != "assembled":
+        raise ValueError(f"preconditioner='multigrid' needs operator='assembled' (got operator={operator!r}); a "
+                         "matrix-free fine level is out of scope")
+    if modulus_scale is not None:
+        raise ValueError("preconditioner='multigrid' has no modulus_scale: the coarse levels are rediscretised with a "
+                         "constant material")
+    if reorder is not None:
+        raise ValueError("preconditioner='multigrid' takes no reorder=: the hierarchy already chose its numbering "
+                         "(refine_c3d4(reorder=...))")
+    if kind not in ("poisson", "elastic"):
+        raise ValueError(f"preconditioner='multigrid' needs kind 'poisson' (bs = 1) or 'elastic' (bs = 3), got {kind!r}")
+    fc, fe = hierarchy.fine
+    dev = fc.device
+    if _dev(device) != dev:
+        raise ValueError(f"preconditioner='multigrid': device={device!r} is not the hierarchy's device {str(dev)!r} "
+                         "(the levels live where refine_c3d4 built them)")
+    if tuple(coords.shape) != tuple(fc.shape) or tuple(elements.shape) != tuple(fe.shape):
+        raise ValueError(f"preconditioner='multigrid': coords / elements must be hierarchy.fine ({list(fc.shape)}, "
+                         f"{list(fe.shape)}), got {list(coords.shape)}, {list(elements.shape)}")
+    with C.device_scope(dev):
+        if not (torch.equal(elements.to(device=dev, dtype=LONG), fe)
+                and torch.equal(coords.to(device=dev, dtype=F64), fc)):
+            raise ValueError("preconditioner='multigrid': coords / elements differ from hierarchy.fine")
+        N = fc.shape[0]
+        dpn = 1 if kind == "poisson" else 3
+        fixed_mask = torch.zeros(N, dtype=torch.bool, device=dev)
+        fixed_mask[torch.as_tensor(fixed).to(device=dev)] = True
+        mg = _sys.Multigrid(hierarchy, kind, E, nu, fixed_mask, degree=mg_degree)
+        b = f.to(device=dev, dtype=F64).reshape(N, dpn).reshape(-1).contiguous().clone()
+        if rtol is not None:
+            tol = float(rtol) * float(torch.sqrt(torch.dot(b, mg.apply(b))))
+        res = mg.pcg(b, None, tol=tol, max_iter=max_iter)
+        res.multigrid = mg
+        return res.x.view(N, dpn), res, mg.fine
+
+
+def multigrid_pcg_solver(hierarchy, F, fixed, kind="elastic", E=1.0, nu=0.0, u_init=None, tol=1e-8, rtol=None,
+                         max_iter=1000, degree=2, eig_iters=10, boost=1.1, ratio=30.0, device=None,
+                         dtype=torch.float64, return_info=False):
+    """PCG on the finest mesh of `hierarchy` (topology.refine_c3d4) with z = one multigrid V(degree, degree) cycle:
+    every level assembled from its own mesh with the constant material (E, nu), Chebyshev-Jacobi smoothing on
+    [lmax boost / ratio, lmax boost] with lmax from `eig_iters` power iterations, a dense solve on level 0. `fixed`
+    are node ids of the finest mesh (hierarchy.carry brings a coarse set there), held at their u_init value, zero by
+    default. Stop on sqrt(r.z) < tol (`rtol`: times sqrt(r0.z0)); prints preconditioned_conjugate_gradient_solver's
+    messages. Returns u [N, dpn] on `device` (default: the hierarchy's, where the solve always runs); with return_info
+    (u, PcgResult) with the system.Multigrid in `.multigrid`, which then lives until its close() or the result is
+    dropped -- without return_info it is closed here."""
+    fc, _ = hierarchy.fine
+    dev = fc.device
+    N = fc.shape[0]
+    dpn = 1 if kind == "poisson" else 3
+    if tuple(F.shape) != (N, dpn):
+        raise ValueError(f"multigrid_pcg_solver: F must be [{N}, {dpn}], got {list(F.shape)}")
+    with C.device_scope(dev):
+        fixed_mask = torch.zeros(N, dtype=torch.bool, device=dev)
+        if fixed is not None:
+            fixed_mask[torch.as_tensor(fixed).to(device=dev, dtype=LONG)] = True
+        mg = _sys.Multigrid(hierarchy, kind, E, nu, fixed_mask, degree=degree, eig_iters=eig_iters, boost=boost,
+                            ratio=ratio)
+        b = F.to(device=dev, dtype=F64).reshape(-1).contiguous()
+        x0 = None if u_init is None else u_init.to(device=dev, dtype=F64).reshape(-1).contiguous()
+        if rtol is not None:
+            r0 = b if x0 is None else b - mg.fine.matvec(x0)
+            tol = float(rtol) * float(torch.sqrt(torch.dot(r0, mg.apply(r0))))
+        res = mg.pcg(b, x0, tol=tol, max_iter=max_iter)
+        res.multigrid = mg
+        _pcg_messages(res)
+        out_dev = dev if device is None else torch.device(device)
+        u = res.x.view(N, dpn).to(device=out_dev, dtype=dtype)
+        if return_info:   # the caller owns the Multigrid (res.multigrid.close() releases the context)
+            return u, res
+        mg.close()
+        return u
 
 
 # ============================================================================ two-level PCG

@@ -2837,6 +2837,265 @@ def assemble_tet4_system(coords, elements, kind="poisson", E=1.0, nu=0.0, graph=
     return A
 
 
+# ============================================================================ geometric multigrid (csrc/multigrid.hip)
+MG_COARSE_CAP = 3072   # free dofs of the coarsest level's dense inverse (the m the two-level PCG allows)
+
+
+def chebyshev_scalars(lmax, degree, boost=1.1, ratio=30.0):
+    """(c1 [degree], c2 [degree]) of the Chebyshev smoother on [lmax boost / ratio, lmax boost] in the residual-update
+    form d_k = c1[k] d_{k-1} + c2[k] w o r_k: theta, delta the interval's centre and half width, sigma = theta /
+    delta, rho_0 = 1 / sigma, rho_k = 1 / (2 sigma - rho_{k-1}); c1[0] = 0, c2[0] = 1 / theta, c1[k] = rho_k rho_{k-1},
+    c2[k] = 2 rho_k / delta. Host floats."""
+    hi = float(lmax) * float(boost)
+    lo = hi / float(ratio)
+    theta, delta = 0.5 * (hi + lo), 0.5 * (hi - lo)
+    sigma = theta / delta
+    rho = 1.0 / sigma
+    c1, c2 = [0.0], [1.0 / theta]
+    for _ in range(1, int(degree)):
+        rho_new = 1.0 / (2.0 * sigma - rho)
+        c1.append(rho_new * rho)
+        c2.append(2.0 * rho_new / delta)
+        rho = rho_new
+    return c1, c2
+
+
+def power_start(n, device="cpu"):
+    """The power iteration's start vector: a fixed hash of the dof index in (-0.5, 0.5) -- no generator state."""
+    i = torch.arange(n, dtype=I64, device=device)
+    return ((i * 2654435761) % 4294967296).to(F64) / 4294967296.0 - 0.5
+
+
+class Multigrid:
+    """Geometric multigrid preconditioner on a topology.MeshHierarchy: one assembled SellMatrix per level (for nested
+    P1 spaces and a constant material the rediscretised coarse matrix is the Galerkin product), masked Jacobi weights,
+    lmax of diag(w) A per level from `eig_iters` power iterations (power_start, the existing SpMV, torch's
+    fixed-order sums), the Chebyshev scalars, the child lists of the restriction and the dense inverse of the coarsest
+    level's free block. `fixed_mask` [N_fine] bool marks the fixed nodes of the finest level; a node of a lower level
+    is fixed iff the finest node it is carried over to is. z = apply(r) is one V(degree, degree) cycle; pcg() is
+    MODE_PCG's iteration with that z. `times`: the setup's synchronised wall milliseconds {"assemble", "eig",
+    "coarse"}. `assemble(level, coords, elements) -> SellMatrix` replaces assemble_tet4_system (a caller's own element
+    matrices or column format). ValueError for a kind other than "poisson" / "elastic", more than MG_COARSE_CAP free dofs on level 0
+    and a coarsest matrix that is not positive definite."""
+
+    def __init__(self, hierarchy, kind="elastic", E=1.0, nu=0.0, fixed_mask=None, degree=2, eig_iters=10, boost=1.1,
+                 ratio=30.0, assemble=None):
+        import time
+        if kind not in ("poisson", "elastic"):
+            raise ValueError(f"Multigrid: kind must be 'poisson' (bs = 1) or 'elastic' (bs = 3), got {kind!r}")
+        if len(hierarchy.levels) < 2:
+            raise ValueError("Multigrid: the hierarchy needs at least one refined level")
+        if not 1 <= int(degree) <= 8:
+            raise ValueError(f"Multigrid: degree 1 to 8, got {degree}")
+        self.h = ctypes.c_void_p()
+        self.hierarchy, self.kind, self.degree = hierarchy, kind, int(degree)
+        self.eig_iters, self.boost, self.ratio = int(eig_iters), float(boost), float(ratio)
+        self.bs = bs = 1 if kind == "poisson" else 3
+        lv = hierarchy.levels
+        self.device = dev = lv[-1].coords.device
+        L = len(lv)
+        with C.device_scope(dev):
+            lib = C.lib()
+            Nf = lv[-1].n_nodes
+            fixed = (torch.zeros(Nf, dtype=torch.bool, device=dev) if fixed_mask is None
+                     else fixed_mask.to(device=dev, dtype=torch.bool).view(-1))
+            if fixed.numel() != Nf:
+                raise ValueError(f"Multigrid: fixed_mask must hold {Nf} values, got {fixed.numel()}")
+            masks = [None] * L
+            masks[-1] = fixed
+            for l in range(L - 1, 0, -1):   # a carried-over node hands its state down
+                p = lv[l].parents.long()
+                carried = p[:, 0] == p[:, 1]
+                m = torch.zeros(lv[l - 1].n_nodes, dtype=torch.bool, device=dev)
+                m[p[carried, 0]] = masks[l][carried]
+                masks[l - 1] = m
+            free0 = bs * int((~masks[0]).sum())
+            if free0 > MG_COARSE_CAP:
+                raise ValueError(f"Multigrid: level 0 has {free0} free dofs, the dense coarse solve is capped at "
+                                 f"{MG_COARSE_CAP}: start from a coarser mesh or add a level")
+            if free0 == 0:
+                raise ValueError("Multigrid: level 0 has no free dof")
+
+            def tick():
+                torch.cuda.synchronize(dev)
+                return time.perf_counter()
+
+            t0 = tick()
+            self.A, self.w, self.masks = [], [], masks
+            for l in range(L):
+                A = (assemble_tet4_system(lv[l].coords, lv[l].elements, kind, E, nu) if assemble is None
+                     else assemble(l, lv[l].coords, lv[l].elements))
+                if A.bs != bs or A.n_rows != lv[l].n_nodes:
+                    raise ValueError(f"Multigrid: level {l} needs a bs = {bs} matrix of {lv[l].n_nodes} block rows")
+                A.check_singular()
+                A.plain_values()
+                mask = torch.zeros((lv[l].n_nodes, bs), dtype=torch.uint8, device=dev)
+                mask[masks[l]] = 1
+                self.A.append(A)
+                self.w.append(A.jacobi(mask.view(-1)))
+            t1 = tick()
+            self.lmax = [None] + [self._lmax(self.A[l], self.w[l]) for l in range(1, L)]
+            c1, c2 = [0.0] * self.degree, [0.0] * self.degree
+            for l in range(1, L):
+                a, b = chebyshev_scalars(self.lmax[l], self.degree, self.boost, self.ratio)
+                c1 += a
+                c2 += b
+            t2 = tick()
+            self.Einv = self._coarse_inverse(self.A[0], masks[0])
+            self.child_ptr, self.child = [None], [None]
+            for l in range(1, L):
+                flat = lv[l].parents.long().view(-1)
+                order = torch.sort(flat, stable=True).indices   # by coarse node, the fine ids ascending inside
+                self.child.append((order // 2).to(I32).contiguous())
+                ptr = torch.zeros(lv[l - 1].n_nodes + 1, dtype=I32, device=dev)
+                ptr[1:] = torch.cumsum(torch.bincount(flat, minlength=lv[l - 1].n_nodes), 0).to(I32)
+                self.child_ptr.append(ptr)
+            t3 = tick()
+            self.times = {"assemble": (t1 - t0) * 1e3, "eig": (t2 - t1) * 1e3, "coarse": (t3 - t2) * 1e3}
+
+            def arr(ts):
+                return (ctypes.c_void_p * L)(*[None if t is None else t.data_ptr() for t in ts])
+
+            nrows = (ctypes.c_int64 * L)(*[x.n_nodes for x in lv])
+            self._c1 = (ctypes.c_double * (L * self.degree))(*c1)
+            self._c2 = (ctypes.c_double * (L * self.degree))(*c2)
+            self._keep = [A.plain_values() for A in self.A]
+            C.check(lib.fem_mg_create(
+                L, bs, nrows, arr([A.g.slice_ptr for A in self.A]), arr([A.g.cols for A in self.A]),
+                arr([A.g.dcols if A.use16 else None for A in self.A]), arr(self._keep), arr(self.w),
+                arr([x.parents for x in lv]), arr(self.child_ptr), arr(self.child), self.degree, self._c1, self._c2,
+                bs * lv[0].n_nodes, C.ptr(self.Einv), C.stream(dev), ctypes.byref(self.h)), "fem_mg_create")
+
+    @property
+    def fine(self):
+        return self.A[-1]
+
+    def _lmax(self, A, w):
+        x = power_start(A.n, self.device) * (w != 0).to(F64)
+        x = x / torch.sqrt((x * x).sum())
+        lam = 0.0
+        for _ in range(self.eig_iters):
+            y = w * A.matvec(x)
+            lam = float((x * y).sum())
+            x = y / torch.sqrt((y * y).sum())
+        if not lam > 0.0:
+            raise ValueError(f"Multigrid: the power iteration gave lmax = {lam} (is the matrix positive definite?)")
+        return lam
+
+    def _coarse_inverse(self, A, fixed):
+        """[m0, m0]: the inverse of the coarsest matrix on its free dofs (Cholesky on the device, symmetrised), zero
+        rows and columns at the fixed ones."""
+        dev, bs, N = self.device, self.bs, A.n_rows
+        rowptr, colidx, vals = A.csr()
+        rows = torch.repeat_interleave(torch.arange(N, device=dev), (rowptr[1:] - rowptr[:-1]).long())
+        D = torch.zeros((N, N, bs, bs), dtype=F64, device=dev)
+        D[rows, colidx.long()[: rows.numel()]] = vals
+        D = D.permute(0, 2, 1, 3).reshape(N * bs, N * bs)
+        f = torch.nonzero((~fixed)[:, None].expand(N, bs).reshape(-1)).view(-1)
+        Aff = D[f][:, f]
+        Aff = 0.5 * (Aff + Aff.T)
+        Lc, info = torch.linalg.cholesky_ex(Aff)
+        if int(info) != 0 or not bool(torch.isfinite(Lc).all()):
+            raise ValueError(f"Multigrid: the coarsest level's matrix is not positive definite on its free dofs "
+                             f"(pivot {int(info) - 1}); is the mesh clamped?")
+        I = torch.cholesky_solve(torch.eye(f.numel(), dtype=F64, device=dev), Lc)
+        Einv = torch.zeros((N * bs, N * bs), dtype=F64, device=dev)
+        Einv[f[:, None], f[None, :]] = 0.5 * (I + I.T)
+        return Einv.contiguous()
+
+    def _vec(self, v, what):
+        v = v.to(device=self.device, dtype=F64).contiguous().view(-1)
+        if v.numel() != self.fine.n:
+            raise ValueError(f"Multigrid: {what} must hold {self.fine.n} values, got {v.numel()}")
+        return v
+
+    def levels_info(self):
+        """One dict per level: nodes, elements, dofs, free dofs, lmax of diag(w) A (None on level 0), the column
+        format."""
+        return [{"level": l, "nodes": A.n_rows, "elements": int(self.hierarchy.levels[l].elements.shape[0]),
+                 "dofs": A.n, "free_dofs": int((self.w[l] != 0).sum()), "lmax": self.lmax[l],
+                 "columns": "delta16" if A.use16 else "int32"} for l, A in enumerate(self.A)]
+
+    def restrict(self, level, r):
+        """P^T (mask o r) from `level` to level - 1 (the restriction kernel alone)."""
+        with C.device_scope(self.device):
+            A, Ac = self.A[level], self.A[level - 1]
+            r = r.to(device=self.device, dtype=F64).contiguous().view(-1)
+            if r.numel() != A.n:
+                raise ValueError(f"Multigrid.restrict: r must hold {A.n} values, got {r.numel()}")
+            rc = torch.empty(Ac.n, dtype=F64, device=self.device)
+            C.check(C.lib().fem_mg_restrict(Ac.n_rows, A.n_rows, self.bs, C.ptr(self.child_ptr[level]),
+                                            C.ptr(self.child[level]), C.ptr(self.w[level]), C.ptr(r), C.ptr(rc),
+                                            C.stream(self.device)), "fem_mg_restrict")
+            return rc
+
+    def prolong(self, level, xc, xf=None):
+        """xf + mask o P xc from level - 1 to `level` (the prolongation kernel alone; xf defaults to zero)."""
+        with C.device_scope(self.device):
+            A, Ac = self.A[level], self.A[level - 1]
+            xc = xc.to(device=self.device, dtype=F64).contiguous().view(-1)
+            if xc.numel() != Ac.n:
+                raise ValueError(f"Multigrid.prolong: xc must hold {Ac.n} values, got {xc.numel()}")
+            out = (torch.zeros(A.n, dtype=F64, device=self.device) if xf is None
+                   else xf.to(device=self.device, dtype=F64).clone().contiguous().view(-1))
+            C.check(C.lib().fem_mg_prolong(A.n_rows, Ac.n_rows, self.bs, C.ptr(self.hierarchy.levels[level].parents),
+                                           C.ptr(self.w[level]), C.ptr(xc), C.ptr(out), C.stream(self.device)),
+                    "fem_mg_prolong")
+            return out
+
+    def sweep(self, level=None):
+        """One fused Chebyshev sweep on the context's work vectors of `level` (default: the finest) -- for timing the
+        kernel; the vectors are scratch that every cycle rewrites."""
+        level = len(self.A) - 1 if level is None else int(level)
+        with C.device_scope(self.device):
+            C.check(C.lib().fem_mg_sweep(self.h, level), "fem_mg_sweep")
+
+    def algorithmic_bytes_sweep(self, level=None):
+        """HBM bytes one fused sweep must move: the matrix once (values, column indices, slice pointers, as
+        SellMatrix.algorithmic_bytes_spmv counts them) plus seven vectors of the level -- d_old, r, w, x read and r,
+        d_new, x written."""
+        A = self.A[len(self.A) - 1 if level is None else int(level)]
+        return A.algorithmic_bytes_spmv() - 16 * A.n + 7 * 8 * A.n
+
+    def apply(self, r):
+        """z = one V-cycle on r."""
+        with C.device_scope(self.device):
+            r = self._vec(r, "r")
+            z = torch.empty_like(r)
+            C.check(C.lib().fem_mg_apply(self.h, C.ptr(r), C.ptr(z)), "fem_mg_apply")
+            return z
+
+    def pcg(self, b, x0=None, tol=1e-8, max_iter=1000, history=False, chunk=8):
+        """PCG on the finest matrix with z = V-cycle(r): MODE_PCG's semantics (stop on sqrt(r.z) < tol, history of
+        sqrt(r.z)), PCG_BREAKDOWN on p.Ap <= 0 or non-finite (x untouched by that iteration) and on r.z <= 0 or
+        non-finite. Returns a PcgResult."""
+        with C.device_scope(self.device):
+            lib = C.lib()
+            b = self._vec(b, "b")
+            x = (torch.zeros_like(b) if x0 is None else self._vec(x0, "x0").clone())
+            hist = torch.full((max(max_iter, 1),), float("nan"), dtype=F64, device=self.device) if history else None
+            it, stt, rz = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+            C.check(lib.fem_mg_solve(self.h, C.ptr(b), C.ptr(x), float(tol), int(max_iter), int(chunk), C.ptr(hist),
+                                     hist.numel() if hist is not None else 0, ctypes.byref(it), ctypes.byref(stt),
+                                     ctypes.byref(rz)), "fem_mg_solve")
+            sc = (ctypes.c_double * 6)()
+            C.check(lib.fem_mg_scalars(self.h, sc), "fem_mg_scalars")
+            if hist is not None:
+                hist = hist[: min(it.value, hist.numel())]
+            return PcgResult(x, it.value, stt.value, rz.value, sc[1], hist)
+
+    def close(self):
+        if self.h:
+            C.lib().fem_mg_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ============================================================================ topology optimisation (csrc/topopt.hip)
 TOPOPT_OK, TOPOPT_MAX_ITER, TOPOPT_LINEAR_SOLVE_FAILED = "OK", "MAX_ITER", "LINEAR_SOLVE_FAILED"
 OC_BISECTIONS = 60

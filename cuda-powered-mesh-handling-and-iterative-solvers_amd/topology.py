@@ -312,7 +312,188 @@ def to_c3d4(elements, device="cuda:0"):
     return None
 
 
+# ---------------------------------------------------------------- mid-edge nodes, uniform refinement (csrc/refine.hip)
+TET10_WALK = [[0, 1], [1, 2], [2, 0], [0, 3], [1, 3], [2, 3]]   # edges of c3d10 nodes 4..9, `:826-831`
+
+
+def _mid_edges(el, dev, first_encounter):
+    """(unique edges [E, 2] lexicographic, eid [6 M] int32: the edge of slot 6 e + k of TET10_WALK, mid_id [E]: the
+    rank of the edge among the mid nodes -- by the lowest slot naming it (the reference's first-encounter order) or
+    the sorted-edge order)."""
+    lib = C.lib()
+    g = FaceGroups(el, EDGES, dev)
+    ue = g.unique().contiguous()
+    g.close()
+    M, E = el.shape[0], ue.shape[0]
+    eid = torch.empty(6 * M, dtype=I32, device=dev)
+    minslot = torch.full((E,), torch.iinfo(torch.int64).max, dtype=LONG, device=dev)
+    C.check(lib.fem_refine_edge_slots(C.ptr(el), M, C.ptr(ue), E, C.ptr(eid), C.ptr(minslot), C.stream(dev)),
+            "fem_refine_edge_slots")
+    if M and int(eid.min()) < 0:
+        raise ValueError("c3d4 mid-edge nodes: an element edge is missing from the mesh's edge list")
+    mid_id = torch.arange(E, dtype=LONG, device=dev)
+    if first_encounter:
+        order = torch.argsort(minslot)   # the slots are distinct
+        mid_id = torch.empty_like(order)
+        mid_id[order] = torch.arange(E, dtype=LONG, device=dev)
+    return ue, eid, mid_id
+
+
+def _elevate(X, el, dev, first_encounter):
+    """c3d4 -> c3d10 on the device: (coords [N + E, 3] fp64, c3d10 connectivity [M, 10], parents [N + E, 2] int32,
+    unique edges, mid_id)."""
+    lib = C.lib()
+    N, M = X.shape[0], el.shape[0]
+    _sys.check_connectivity(el, N)
+    ue, eid, mid_id = _mid_edges(el, dev, first_encounter)
+    E = ue.shape[0]
+    if N + E > torch.iinfo(torch.int32).max:
+        raise ValueError(f"c3d4 mid-edge nodes: {N + E} nodes do not fit int32 ids")
+    el10 = torch.empty((M, 10), dtype=LONG, device=dev)
+    C.check(lib.fem_refine_emit(C.ptr(el), M, N, C.ptr(eid), C.ptr(mid_id), C.ptr(el10), C.stream(dev)),
+            "fem_refine_emit")
+    Xo = torch.empty((N + E, 3), dtype=F64, device=dev)
+    parents = torch.empty((N + E, 2), dtype=I32, device=dev)
+    C.check(lib.fem_refine_nodes(C.ptr(X), N, C.ptr(ue), E, C.ptr(mid_id), C.ptr(Xo), C.ptr(parents), C.stream(dev)),
+            "fem_refine_nodes")
+    return Xo, el10, parents, ue, mid_id
+
+
+def _node_set(ids, N, dev):
+    """bool [N] mask of a node id list; IndexError for an id outside [0, N) (checked on the host: an index kernel
+    must never see one)."""
+    ids = torch.as_tensor(ids).to(device=dev, dtype=LONG).view(-1)
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= N):
+        raise IndexError(f"node ids must be in [0, {N})")
+    inside = torch.zeros(N, dtype=torch.bool, device=dev)
+    inside[ids] = True
+    return inside
+
+
+def _carry_ids(ids, N, ue, mid_id, dev):
+    """A node set after the elevation: its nodes plus every mid node with both ends in it, sorted (`:817-820`)."""
+    if ids is None:
+        return torch.empty(0, dtype=LONG, device=dev)
+    inside = _node_set(ids, N, dev)
+    both = inside[ue[:, 0]] & inside[ue[:, 1]]
+    return torch.sort(torch.cat([torch.nonzero(inside).view(-1), N + mid_id[both]])).values
+
+
+def c3d4_to_c3d10(coords, elements, rbe2_ids=None, rbe3_ids=None, dtype=torch.float32, device="cuda:0"):
+    """Quadratic tets from linear ones (`solver/element.py:777-833`): (coords [N + E, 3] in `dtype`, connectivity
+    [M, 10] int32, rbe2 ids, rbe3 ids int32). Mid-edge nodes follow the corner nodes in first-encounter order of the
+    walk element by element over edges (0,1), (1,2), (2,0), (0,3), (1,3), (2,3); a mid node joins a set when both ends
+    are in it (the sets come back sorted; the reference returns them in hash order). A mid coordinate is
+    (cA + cB) / 2 evaluated in fp64 and rounded once to `dtype`, as the reference's Python floats are -- for coordinates
+    already in `dtype` that is the sum evaluated in `dtype`."""
+    dev = _dev(device)
+    X = coords.to(device=dev, dtype=F64).contiguous()
+    el = elements.to(device=dev, dtype=LONG).contiguous()
+    if el.dim() != 2 or el.shape[1] != 4 or X.dim() != 2 or X.shape[1] != 3:
+        raise ValueError(f"c3d4_to_c3d10: coords [N, 3] and elements [M, 4] are needed, got {list(X.shape)} and "
+                         f"{list(el.shape)}")
+    Xo, el10, _, ue, mid_id = _elevate(X, el, dev, True)
+    N = X.shape[0]
+    r2, r3 = (_carry_ids(ids, N, ue, mid_id, dev).to(I32) for ids in (rbe2_ids, rbe3_ids))
+    return (_out(Xo.to(dtype), device), _out(el10.to(I32), device), _out(r2, device), _out(r3, device))
+
+
+def refinement_table():
+    """The 8-child table of the uniform (red) refinement: SPLIT[10] with every child oriented like its parent. The
+    orientation of the children of the unit tet is checked here, on the host; a child the table leaves negative gets
+    its last two nodes exchanged in the copy returned (SPLIT itself is not touched)."""
+    c = torch.tensor([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], dtype=F64)
+    x = torch.cat([c, torch.stack([0.5 * (c[a] + c[b]) for a, b in TET10_WALK])])
+    tab = [list(r) for r in SPLIT[10]]
+    for row in tab:
+        p = x[row]
+        if float(torch.linalg.det(p[1:] - p[0])) < 0:
+            row[2], row[3] = row[3], row[2]
+    return tab
+
+
+class MeshLevel:
+    """One level of a MeshHierarchy: coords [N, 3] fp64, elements [M, 4] int64, parents [N, 2] int32 (ids of the level
+    below in its numbering, a == b for a carried-over node; None on level 0) and perm [N] (the level's node k is node
+    perm[k] of the numbering reorder=None gives; None when the level was not renumbered)."""
+
+    def __init__(self, coords, elements, parents=None, perm=None):
+        self.coords, self.elements, self.parents, self.perm = coords, elements, parents, perm
+
+    @property
+    def n_nodes(self):
+        return int(self.coords.shape[0])
+
+
+class MeshHierarchy:
+    """Nested c3d4 meshes from refine_c3d4: `levels[0]` the caller's mesh, `levels[-1]` the finest."""
+
+    def __init__(self, levels, reorder):
+        self.levels, self.reorder = levels, reorder
+        self.device = levels[0].coords.device
+
+    def __len__(self):
+        return len(self.levels)
+
+    @property
+    def fine(self):
+        last = self.levels[-1]
+        return last.coords, last.elements
+
+    def carry(self, node_ids, level=None):
+        """A node set of level 0 carried to `level` (default: the finest): a node of level l + 1 is in the set when
+        both its parents are (a carried-over node: when the node itself is). Sorted int64 ids."""
+        level = len(self.levels) - 1 if level is None else int(level)
+        if not 0 <= level < len(self.levels):
+            raise ValueError(f"MeshHierarchy.carry: level {level} of {len(self.levels)}")
+        with C.device_scope(self.device):
+            inside = _node_set(node_ids, self.levels[0].n_nodes, self.device)
+            for lv in self.levels[1:level + 1]:
+                p = lv.parents.long()
+                inside = inside[p[:, 0]] & inside[p[:, 1]]
+            return torch.nonzero(inside).view(-1)
+
+
+def refine_c3d4(coords, elements, levels=1, reorder="rcm", device=None):
+    """Uniform (red) refinement of a c3d4 mesh, `levels` times -> MeshHierarchy. Level l + 1 is the c3d10 elevation of
+    level l split by refinement_table() (four corner tets, the inner octahedron cut along mid(1,2)-mid(0,3)); the
+    coordinates are fp64 and a mid node is one rounded 0.5 (a + b). reorder="rcm" (default) renumbers every refined
+    level with system.rcm_order -- appended mid nodes would push the fine matrix off the 16-bit column-delta SELL path
+    -- and `parents` absorbs the permutation; reorder=None keeps the corner nodes first and the mid nodes in
+    sorted-edge order. `device`: default the coordinates' device when that is a HIP device, else the current one."""
+    if reorder not in (None, "rcm"):
+        raise ValueError(f"unknown reorder {reorder!r} (supported: 'rcm', None)")
+    levels = int(levels)
+    if levels < 1:
+        raise ValueError(f"refine_c3d4: levels must be >= 1, got {levels}")
+    dev = _dev(device if device is not None else coords.device)
+    with C.device_scope(dev):
+        lib = C.lib()
+        X = coords.to(device=dev, dtype=F64).contiguous()
+        el = elements.to(device=dev, dtype=LONG).contiguous()
+        if el.dim() != 2 or el.shape[1] != 4 or X.dim() != 2 or X.shape[1] != 3:
+            raise ValueError(f"refine_c3d4: coords [N, 3] and elements [M, 4] are needed, got {list(X.shape)} and "
+                             f"{list(el.shape)}")
+        tab = _i32(refinement_table())
+        out = [MeshLevel(X, el)]
+        for _ in range(levels):
+            Xo, el10, parents, _, _ = _elevate(X, el, dev, False)
+            M = el10.shape[0]
+            fine = torch.empty((8 * M, 4), dtype=LONG, device=dev)
+            C.check(lib.fem_sub_elements(C.ptr(el10), M, 10, tab, 8, 4, C.ptr(fine), C.stream(dev)),
+                    "fem_sub_elements")
+            perm = None
+            if reorder == "rcm":
+                perm, inv = _sys.rcm_order(fine, Xo.shape[0])
+                Xo, fine = _sys.renumber(Xo, fine, perm, inv)
+                Xo, fine, parents = Xo.contiguous(), fine.contiguous(), parents[perm].contiguous()
+            out.append(MeshLevel(Xo, fine, parents, perm))
+            X, el = Xo, fine
+        return MeshHierarchy(out, reorder)
+
+
 __all__ = [
+    "c3d4_to_c3d10", "refine_c3d4", "refinement_table", "MeshHierarchy", "MeshLevel",
     "compute_tetrahedral_surface_faces_with_fourth_node", "compute_hexahedral_surface_faces_with_extra_node",
     "compute_wedge_surface_faces_with_extra_node", "compute_tetrahdral_surface_normals",
     "compute_tetrahedral_surface_normals", "compute_hexahedral_surface_normals", "compute_wedge_surface_normals",

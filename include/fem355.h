@@ -873,6 +873,58 @@ int fem_pcg2_solve(fem_pcg2* s, int max_iter, int chunk, int* iters, int* status
 int fem_pcg2_scalars(fem_pcg2* s, double* out6);
 void fem_pcg2_destroy(fem_pcg2* s);
 
+/* ------------------------------------------------------------------ mid-edge nodes of c3d4 meshes (csrc/refine.hip)
+ * The device side of c3d4_to_c3d10 and refine_c3d4. uedges [E, 2] are the mesh's distinct edges (a < b, lexicographic:
+ * fem_topo_unique on the six-edge table). Element e meets its edges in the walk (0,1), (1,2), (2,0), (0,3), (1,3),
+ * (2,3): slot 6 e + k.
+ * fem_refine_edge_slots: eid [6 M] int32 = the slot's edge (-1: not in the list), minslot [E] (preset to INT64_MAX by
+ *   the caller) = the lowest slot naming the edge (integer minimum: independent of the order of arrival).
+ * fem_refine_emit: out [M, 10] = the four corners, then N + mid_id[eid[slot]] in walk order (c3d10 node order).
+ * fem_refine_nodes: coords_out [N + E, 3] and parents [N + E, 2] int32: node i < N is itself (parents i, i), node
+ *   N + mid_id[j] is 0.5 (x[a] + x[b]) of edge j = (a, b), one rounding (parents a, b). N + E must fit int32. */
+int fem_refine_edge_slots(const int64_t* conn, int64_t M, const int64_t* uedges, int64_t E, int32_t* eid,
+                          int64_t* minslot, fem_stream_t stream);
+int fem_refine_emit(const int64_t* conn, int64_t M, int64_t N, const int32_t* eid, const int64_t* mid_id, int64_t* out,
+                    fem_stream_t stream);
+int fem_refine_nodes(const double* coords, int64_t N, const int64_t* uedges, int64_t E, const int64_t* mid_id,
+                     double* coords_out, int32_t* parents, fem_stream_t stream);
+
+/* ------------------------------------------------------------------ geometric multigrid PCG (csrc/multigrid.hip)
+ * PCG with z = one V(degree, degree) cycle over nlev >= 2 nested levels, level 0 the coarsest, level nlev - 1 the
+ * matrix being solved. Every per-level argument is a host array of nlev device pointers: the level's plain SELL-64
+ * matrix (slice_ptr, cols or 16-bit dcols, vals; bs = 1 or 3 on all levels; unused on level 0), its masked Jacobi
+ * weights w (zero on the fixed dofs) and, above level 0, parents [N_l, 2] int32 (node i = 0.5 (a + b) of level l - 1,
+ * a == b for a carried node) with the child lists child_ptr [N_{l-1} + 1] / child (the nodes of level l that name
+ * node c of level l - 1, ascending, once per occurrence). c1 / c2 [nlev, degree] are the Chebyshev scalars of
+ * diag(w) A per level and sweep (c1[., 0] = 0), Einv [m0, m0] with m0 = bs N_0 the dense inverse of the masked
+ * coarsest matrix (zero rows and columns at its fixed dofs). Plain launches, no floating-point atomics, every sum in
+ * an order fixed by the sizes alone, rows >= nrows never read or stored.
+ * fem_mg_restrict / fem_mg_prolong: the transfer kernels alone, rc = P^T (mask_f o rf) and xf += mask_f o P xc.
+ * fem_mg_apply: z = cycle(r) on the context's stream (r is not written).
+ * fem_mg_solve [sync]: FEM_MODE_PCG's iteration from the x in place with that z: stop on sqrt(r.z) < tol, hist
+ *   [hist_len] (may be NULL) receives sqrt(r.z); FEM_PCG_BREAKDOWN on p.Ap <= 0 or non-finite (x is then not updated
+ *   in that iteration) and on r.z <= 0 or non-finite (an underestimated lmax can make the cycle indefinite; r0.z0 < 0
+ *   is reported as iteration 1). r0.z0 == 0 (b = 0 with x = 0: the start vector solves the free rows) is
+ *   FEM_PCG_CONVERGED with 0 iterations and x untouched, where FEM_MODE_PCG's alpha would be 0 / 0. The host
+ *   enqueues `chunk` iterations at a time and reads the state in between. */
+typedef struct fem_mg fem_mg;
+int fem_mg_restrict(int64_t nc, int64_t nf, int bs, const int32_t* child_ptr, const int32_t* child, const double* wf,
+                    const double* rf, double* rc, fem_stream_t stream);
+int fem_mg_prolong(int64_t nf, int64_t nc, int bs, const int32_t* parents, const double* wf, const double* xc,
+                   double* xf, fem_stream_t stream);
+int fem_mg_create(int nlev, int bs, const int64_t* nrows, const void* const* slice_ptr, const void* const* cols,
+                  const void* const* dcols, const void* const* vals, const void* const* w, const void* const* parents,
+                  const void* const* child_ptr, const void* const* child, int degree, const double* c1,
+                  const double* c2, int64_t m0, const double* Einv, fem_stream_t stream, fem_mg** out);
+int fem_mg_apply(fem_mg* s, const double* r, double* z);
+/* one fused Chebyshev sweep on the work vectors of `level` >= 1 (timing only: the vectors' contents are scratch) */
+int fem_mg_sweep(fem_mg* s, int level);
+int fem_mg_solve(fem_mg* s, const double* b, double* x, double tol, int max_iter, int chunk, double* hist,
+                 int64_t hist_len, int* iters, int* status, double* rz);
+/* [sync] fem_pcg_scalars' six values */
+int fem_mg_scalars(fem_mg* s, double* out6);
+void fem_mg_destroy(fem_mg* s);
+
 /* ------------------------------------------------------------------ modal analysis (csrc/modal.hip)
  * The tall-skinny kernels of the block LOBPCG that SellMatrix.eig_lowest drives for the lowest eigenpairs of
  * K u = lambda M u. Multi-vectors are [n, nv] row-major as above (nv 2, 4 or 8; 16-byte aligned). Plain launches;
