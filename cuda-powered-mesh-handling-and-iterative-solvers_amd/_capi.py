@@ -30,7 +30,9 @@ TUNE_MF_GATHER = 8192   # element-chunk operator: q summed by a gather launch in
 TUNE_PK_GV = 16384      # persistent schedule, small bs = 1 systems: the pipelined (Ghysels-Vanroose) iteration
 TUNE_PK_OFFDIAG = 32768  # persistent schedule, bs = 1: the diagonal kept on chip, off-diagonal values streamed
 TUNE_PK_DESC = 65536     # ... and each slice's header and delta list read from one record by scalar loads
-TUNE_DEFAULT = 1 | 2 | 4 | 8 | 128 | TUNE_UPD1 | TUNE_PK_OFFDIAG | TUNE_PK_DESC
+TUNE_PK_GRAN = 131072    # ... and d, g reduced through tagged granules instead of the counter grid barrier
+TUNE_PK_GRAN_SMALL = 262144   # opt-in: ... in the two- and four-slot builds too (measured slower / no faster there)
+TUNE_DEFAULT = 1 | 2 | 4 | 8 | 128 | TUNE_UPD1 | TUNE_PK_OFFDIAG | TUNE_PK_DESC | TUNE_PK_GRAN
 KIND_ELASTIC, KIND_POISSON, KIND_MASS = 0, 1, 2
 ISO_SUM, ISO_STACK, ISO_VOLUME, ISO_MASS = 0, 1, 2, 3
 MASS_SELL, MASS_DIAG = 0, 1   # include/fem355.h fem_mass_form
@@ -144,6 +146,7 @@ SIGNATURES = {
     "fem_pcg_desc_slices": (_I, [_P, _P, _P]),
     "fem_pcg_debug_desc": (_I, [_P, _P]),
     "fem_pcg_persist_build": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "fem_pcg_persist_granules": (_I, [_P, ctypes.POINTER(_I)]),
     "fem_pcg_pipelined": (_I, [_P, ctypes.POINTER(_I)]),
     "fem_sell_sl_pattern": (_I, [_L, _P, _P, _I, _P, _P, _P, _P, _P]),
     "fem_assemble_tet4_sl": (_I, [_P, _P, _D, _D, _I, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),

@@ -1919,6 +1919,9 @@ struct fem_pcg {
     int32_t* pk_win;      // [2 G]: first workgroups, then last workgroups of the gather windows
     double* pk_part;      // [2][2][G]
     unsigned* pk_sync;    // (18 + G) lines, zeroed before every launch
+    pk_u64* pk_gran;      // granule block of the reduction (pcg_persist_sync.hpp), zeroed wherever pk_sync is
+    int pk_red_kind;      // reduction of the last persistent launch since the sync words were zeroed: 0 none yet,
+                          // 1 counter barrier, 2 granules (launch_persist)
     int pk_ovf;           // overflow build (more than PK_MAXS slices per wave)
     double* pk_v;         // [n] v of the overflow rows
     // diagonal-free value stream (FEM_TUNE_PK_OFFDIAG, sell_pair.hpp k_sell_offdiag): private to this context, always
@@ -2835,13 +2838,15 @@ struct PkBuild {
     const void* fn;
     size_t lds;  // dynamic LDS bytes of a launch
     bool desc;   // slot headers and delta lists from per-slice records (FEM_TUNE_PK_DESC)
+    bool gran;   // d and g reduced through tagged granules (FEM_TUNE_PK_GRAN)
 };
 
 // a row's key and its template arguments come from the same parameters
-template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false, bool OD = false, bool DESC = false>
+template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false, bool OD = false, bool DESC = false,
+          bool GRAN = false>
 static PkBuild pk1_build() {
     return {DIST ? PKF_BS1_DIST : PKF_BS1, MAXS, PROF, GSC1, OVF, DIST, OD,
-            (const void*)k_pcg_persist<MAXS, PROF, GSC1, OVF, DIST, OD, DESC>, PK_LDS, DESC};
+            (const void*)k_pcg_persist<MAXS, PROF, GSC1, OVF, DIST, OD, DESC, GRAN>, PK_LDS, DESC, GRAN};
 }
 template <bool OVF, bool DIST>
 static PkBuild pk3_build() {
@@ -2884,6 +2889,13 @@ static const PkBuild PK_BUILDS[] = {
     pk1_build<4, false, true, false, false, true, true>(),
     pk1_build<PK_MAXS, false, true, false, false, true, true>(),
     pk1_build<PK_MAXS, true, true, false, false, true, true>(),
+    // the builds of the default flag set with the reduction through tagged granules: those five, and the overflow one
+    pk1_build<1, false, true, false, false, true, true, true>(),
+    pk1_build<2, false, true, false, false, true, true, true>(),
+    pk1_build<4, false, true, false, false, true, true, true>(),
+    pk1_build<PK_MAXS, false, true, false, false, true, true, true>(),
+    pk1_build<PK_MAXS, true, true, false, false, true, true, true>(),
+    pk1_build<PK_MAXS, false, true, true, false, true, false, true>(),
     // bs = 1, DIST: always sc1 gathers, never overflow; instrumented forms of the two larger ones only
     pk1_build<1, false, true, false, true>(),
     pk1_build<2, false, true, false, true>(),
@@ -2903,10 +2915,10 @@ static const PkBuild PK_BUILDS[] = {
 };
 
 static const PkBuild* pk_find(PkFamily fam, int slots, bool prof, bool gsc1, bool ovf, bool dist, bool od,
-                              bool desc = false) {
+                              bool desc = false, bool gran = false) {
     for (const PkBuild& b : PK_BUILDS)
         if (b.fam == fam && b.slots == slots && b.prof == prof && b.gsc1 == gsc1 && b.ovf == ovf && b.dist == dist &&
-            b.od == od && b.desc == desc)
+            b.od == od && b.desc == desc && b.gran == gran)
             return &b;
     return nullptr;
 }
@@ -2953,6 +2965,11 @@ static PkPlan persist_plan(const fem_pcg* s, bool prof, bool gv) {
     const bool small = pack >= 1 && pack <= 4 && !(s->tune & FEM_TUNE_PK_WIDE) && !prof && !ovf && gsc1;
     const int slots = !small ? PK_MAXS : pack == 1 ? 1 : pack == 2 ? 2 : 4;
     const bool desc = s->pk_od && s->pk_desc_on && gsc1 && !ovf;   // (no DESC build with plain gathers or overflow)
+    // the granule reduction where a build has it: the rows the default flag set reaches. The two- and four-slot
+    // builds only with FEM_TUNE_PK_GRAN_SMALL as well: measured slower (two slots) or no faster (four) than the counter
+    // barrier
+    if ((s->tune & FEM_TUNE_PK_GRAN) && (slots == 1 || slots == PK_MAXS || (s->tune & FEM_TUNE_PK_GRAN_SMALL)))
+        if (const PkBuild* b = pk_find(PKF_BS1, slots, prof, gsc1, ovf, false, s->pk_od != 0, desc, true)) return {b, pack};
     return {pk_find(PKF_BS1, slots, prof, gsc1, ovf, false, s->pk_od != 0, desc), pack};
 }
 static PkPlan persist_plan(const fem_pcg* s, bool prof) { return persist_plan(s, prof, s->pk_gv && s->bs == 1); }
@@ -3199,7 +3216,7 @@ int fem_pcg_create(int64_t nrows, int bs, const int64_t* slice_ptr, const int32_
     }
     fem_pcg* s = new fem_pcg();
     s->tune = FEM_TUNE_REVERSE | FEM_TUNE_PAIR | FEM_TUNE_PK_SC1 | FEM_TUNE_PK_PACK | FEM_TUNE_PK_UNI | FEM_TUNE_UPD1 |
-              FEM_TUNE_PK_OFFDIAG | FEM_TUNE_PK_DESC;
+              FEM_TUNE_PK_OFFDIAG | FEM_TUNE_PK_DESC | FEM_TUNE_PK_GRAN;
     s->nrows = nrows;
     s->bs = bs;
     s->nslices = cdiv(nrows, 64);
@@ -3625,12 +3642,15 @@ static int persist_setup(fem_pcg* s) {
         pool_free(s->pk_win, s->stream);
         pool_free(s->pk_part, s->stream);
         pool_free(s->pk_sync, s->stream);
+        pool_free(s->pk_gran, s->stream);
         s->pk_win = nullptr;
         s->pk_part = nullptr;
         s->pk_sync = nullptr;
+        s->pk_gran = nullptr;
         FEM_HIP(pool_alloc((void**)&s->pk_win, sizeof(int32_t) * 2 * G, s->stream, s->bs == 1));
         FEM_HIP(pool_alloc((void**)&s->pk_part, sizeof(double) * 4 * G, s->stream, s->bs == 1));
         FEM_HIP(pool_alloc((void**)&s->pk_sync, sizeof(unsigned) * pk_sync_words(G), s->stream, s->bs == 1));
+        FEM_HIP(pool_alloc((void**)&s->pk_gran, sizeof(pk_u64) * pk_gran_words(G), s->stream, s->bs == 1));
         s->pk_grid = G;
         s->pk_win_ok = 0;
     }
@@ -3713,8 +3733,11 @@ static int persist_setup_dist(fem_pcg* s) {
 // one persistent launch of k iterations (schedule 3); prof (device, [G][PK_NPROF]) selects the instrumented build
 static int persist_reset_sync(fem_pcg* s) {
     FEM_HIP(hipMemsetAsync(s->pk_sync, 0, sizeof(unsigned) * pk_sync_words(s->pk_grid), s->stream));
+    // (stale tags of an earlier solve must never match a restarted epoch count)
+    FEM_HIP(hipMemsetAsync(s->pk_gran, 0, sizeof(pk_u64) * pk_gran_words(s->pk_grid), s->stream));
     FEM_HIP(hipMemsetAsync(&s->st->pk_epoch, 0, sizeof(unsigned), s->stream));
     s->pk_epochs = 0;
+    s->pk_red_kind = 0;
     return FEM_OK;
 }
 
@@ -3763,6 +3786,7 @@ static PkArgs pk_args(const fem_pcg* s, const PkPlan& plan, int k, unsigned long
     a.vals_full = s->pvals;
     a.ucol_full = uni ? s->pucol : nullptr;
     a.desc = plan.b->desc ? s->pk_desc : nullptr;
+    a.gran = plan.b->gran ? s->pk_gran : nullptr;
     return a;
 }
 
@@ -3808,6 +3832,16 @@ static int launch_persist(fem_pcg* s, int k, unsigned long long* prof) {
         set_error("persistent PCG: no build for this context (%d slices per wave)", plan.pack);
         return FEM_ESTATE;
     }
+    // fem_pcg_set_tuning between two launches may move the plan between a granule build and a counter build: the
+    // counters (or the tags) did not advance while the other reduction ran, so the epochs start over. Safe between
+    // launches: a launch's first iteration waits on no u-flag and takes g from the state
+    const int red_kind = plan.b->gran ? 2 : 1;
+    if (!s->pd && s->pk_red_kind && s->pk_red_kind != red_kind) {
+        const int rc = persist_reset_sync(s);
+        if (rc) return rc;
+        s->pk_epochs = k + 1;
+    }
+    s->pk_red_kind = red_kind;
     PkArgs a = pk_args(s, plan, k, prof);
     s->pd_init_pending = 0;   // (a.init)
     GvArgs g;
@@ -3833,6 +3867,14 @@ static int launch_persist(fem_pcg* s, int k, unsigned long long* prof) {
 
 int fem_pcg_pipelined(fem_pcg* s, int* on) {
     *on = (s && s->persist && s->pk_gv) ? 1 : 0;
+    return FEM_OK;
+}
+
+int fem_pcg_persist_granules(fem_pcg* s, int* on) {
+    *on = 0;
+    if (!s || !s->persist || s->pk_grid <= 0) return FEM_OK;
+    const PkPlan plan = persist_plan(s, false);   // (the instrumented form of a granule build is one too)
+    *on = (plan.b && plan.b->gran) ? 1 : 0;
     return FEM_OK;
 }
 
@@ -3998,6 +4040,7 @@ int fem_pcg_start(fem_pcg* s) {
             return FEM_EARG;
         }
         FEM_HIP(hipMemsetAsync(s->pk_sync, 0, sizeof(unsigned) * pk_sync_words(s->pk_grid), s->stream));
+        FEM_HIP(hipMemsetAsync(s->pk_gran, 0, sizeof(pk_u64) * pk_gran_words(s->pk_grid), s->stream));
         // the whole comm block, u included: no row of an earlier solve (or a non-finite one) survives into this one
         FEM_HIP(hipMemsetAsync(s->pd_block, 0, (size_t)s->pd_block_bytes, s->stream));
         FEM_HIP(hipMemsetAsync(&s->st->pk_epoch, 0, sizeof(unsigned), s->stream));
@@ -4545,9 +4588,12 @@ int fem_pcg_set_rows(fem_pcg* s, int nranks, int rank, const int64_t* slice_spli
     pool_free(s->pk_win, s->stream);
     pool_free(s->pk_part, s->stream);
     pool_free(s->pk_sync, s->stream);
+    pool_free(s->pk_gran, s->stream);
     FEM_HIP(pool_alloc((void**)&s->pk_win, sizeof(int32_t) * (2 * G + 2), s->stream, true));
     FEM_HIP(pool_alloc((void**)&s->pk_part, sizeof(double) * 4 * G, s->stream, true));
     FEM_HIP(pool_alloc((void**)&s->pk_sync, sizeof(unsigned) * pk_sync_words(G), s->stream, true));
+    FEM_HIP(pool_alloc((void**)&s->pk_gran, sizeof(pk_u64) * pk_gran_words(G), s->stream, true));
+    FEM_HIP(hipMemsetAsync(s->pk_gran, 0, sizeof(pk_u64) * pk_gran_words(G), s->stream));
     s->pk_grid = G;
     std::vector<int32_t> lohi(2 * (size_t)G + 2);
     for (int i = 0; i < G; ++i) {
@@ -4764,6 +4810,7 @@ void fem_pcg_destroy(fem_pcg* s) {
     pool_free(s->pk_win, s->stream);
     pool_free(s->pk_part, s->stream);
     pool_free(s->pk_sync, s->stream);
+    pool_free(s->pk_gran, s->stream);
     pool_free(s->pk_v, s->stream);
     pool_free(s->pk_ovals, s->stream);
     pool_free(s->pk_oucol, s->stream);

@@ -11,9 +11,11 @@
 //              (gather window, computed once per matrix); workgroup barrier (GSC1 = 0: one agent acquire first)
 //     SpMV   : v = A u over the own slices (paired layout; u gathers as global sc1 loads, GSC1 = 1, the default),
 //              d partial = u.v
-//     reduce : workgroup partials of d (and g of the last update) stored sc1 into a parity bank; hierarchical
-//              grid barrier (8 group counters -> 8 replicas of the top counter), wave 0 then sums
-//              the G partials in the same fixed order -> identical scalars in every workgroup
+//     reduce : workgroup partials of d (and g of the last update) as tagged granules in a parity bank; wave 0 of
+//              every workgroup re-reads the records it still misses until all carry the epoch, then sums the G
+//              partials in a fixed order -> identical scalars in every workgroup (FEM_TUNE_PK_GRAN, the default;
+//              pcg_persist_sync.hpp). Without the flag, and in the DIST build: partials stored sc1, hierarchical
+//              grid barrier (8 group counters -> 8 replicas of the top counter), then the same sums
 //     step   : stop test on g (`solver/solver.py:210` / `:805`), beta, p.Ap = d - beta g / alpha_prev, alpha,
 //              guards (`:187-198`, `:214`) -- the single-reduction step (pcg.hip cg1_eval), by every thread
 //     update : p = u + beta p, s = v + beta s, x += alpha p, r -= alpha s (CG: masked), u = w r stored sc1,
@@ -25,157 +27,9 @@
 // Exactly one workgroup of PK_T threads per CU (LDS pins it): the grid is resident by construction (the host
 // checks the occupancy query; a plain launch: a cooperative one adds ~17 us per launch and buys only that check).
 #pragma once
-#include "sell_pair.hpp"
+#include "pcg_persist_sync.hpp"
 
 namespace fem {
-
-// PK_T / PK_WAVES (threads / waves per workgroup) and pk_slice_span live in sell_pair.hpp: the pattern pass that
-// forms the gather windows (sl_pattern_slice) needs them outside this header
-constexpr int PK_MAXS = 7;               // slices per wave (10M Poisson: 27,000 slices over 4,096 waves -> 7)
-constexpr int PK_U = 2;                  // pairs in flight per lane (4 spills the slot state; persist_probe: 4 = 8)
-// pairs in flight of a build: one slot per wave (small systems: every wave owns at most one slice, e.g. 1M tets or
-// a rank's share at N = 8) leaves the registers for 8 pairs, so a slice's loads go out in one round instead of 4;
-// up to four slots for 4 pairs (the instrumented builds keep PK_U there: their clock registers would spill)
-template <int MAXS, bool PROF>
-constexpr int pk_u() { return MAXS <= 1 ? 8 : (MAXS <= 4 && !PROF) ? 4 : PK_U; }
-// pairs in flight of a record slot (DESC builds): the one-slot build takes 4 there, since its 8-pair round beside the
-// 8-pair round of the slices read without a record spills into the SpMV (96 bytes of scratch per lane)
-template <int MAXS, bool PROF>
-constexpr int pk_u_rec() { return MAXS <= 1 ? 4 : pk_u<MAXS, PROF>(); }
-constexpr int PK_LINE = 32;              // unsigned words per 128-byte line
-// sync words (zeroed by fem_pcg_start; epochs continue across launches from PcgState::pk_epoch), in lines: [0, 8) group arrivals, 8 (unused), [9, 17) replicas of the
-// top counter (one per group),
-// 17 give-up word, 18 + L: u-flag of workgroup L
-enum { PK_GRP = 0, PK_TOP = 8 * PK_LINE, PK_GEN = 9 * PK_LINE, PK_TMO = 17 * PK_LINE, PK_UFLAG = 18 * PK_LINE };
-// every spin is bounded in TIME (s_memrealtime, 100 MHz on gfx9 parts: hipDeviceAttributeWallClockRate), checked
-// every 64 polls: 2 s for a wait inside one GPU (the longest legitimate one is a grid barrier behind one ~50 us
-// SpMV phase), 5 s for the rank exchange of the DIST build (ranks start their launches up to milliseconds apart).
-// A give-up therefore costs at most ~5 s per launch whatever the poll latency (xGMI system-scope loads included);
-// the spin-count bound this replaces scaled with that latency (4M polls: 4-50 s)
-constexpr uint64_t PK_WAIT_TICKS = 200000000ull;
-constexpr uint64_t PK_RANK_WAIT_TICKS = 500000000ull;
-__device__ __forceinline__ uint64_t pk_now() { return __builtin_amdgcn_s_memrealtime(); }
-__device__ __forceinline__ bool pk_expired(uint64_t t0, uint64_t ticks) { return pk_now() - t0 > ticks; }
-constexpr int PK_NPROF = 8;   // phases: u wait, SpMV, block sum, barrier + sums, step, update + drain + flag,
-                               // prologue (state loads), epilogue (chunk-end barrier + state stores)
-// dynamic LDS (statics would shift the dynamic base off 16 B, cdna_hip_programming.md Guideline 17): 16 wave sums,
-// the barrier verdict (own 16-byte slot), then x and w of the workgroup's rows
-constexpr size_t PK_LDS_HEAD = 256;
-constexpr int PK_VL = 5;                 // slots of v = A u kept in LDS (the rest in registers): fills the LDS left
-                                         // by x and w, frees 2 PK_VL VGPRs for the SpMV (no spills at PK_U = 2)
-constexpr size_t PK_LDS = PK_LDS_HEAD + sizeof(double) * (2 * PK_MAXS + PK_VL) * PK_WAVES * 64;
-static_assert(PK_LDS <= 160 * 1024, "persistent PCG: LDS over the 160 KB of a CU");
-
-// an opaque copy of a global pointer (the compiler cannot hoist address arithmetic on it out of the iteration loop)
-// that keeps its address space: laundering a generic pointer turns every access through it into a FLAT access
-// (lgkmcnt-coupled, and `flat_` sc1 loads are not a valid hand-off form, MI355X_MICROARCH.md)
-template <class T>
-__device__ __forceinline__ T* pk_launder(T* p) {
-    __attribute__((address_space(1))) T* q = (__attribute__((address_space(1))) T*)p;
-    asm volatile("" : "+s"(q));
-    return (T*)q;
-}
-
-__device__ __forceinline__ unsigned pk_ld(const unsigned* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void pk_st(unsigned* p, unsigned v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// one lane spins until *p >= target; false on give-up (own or another spinner's)
-// the give-up word holds the site of the first give-up (diagnostics, reported by fem_pcg_sync_site for a
-// FEM_PCG_SYNC_TIMEOUT): 1 + 16 * epoch local grid barrier, 2 + 16 * epoch u-flag window, 3 + 16 * epoch
-// rank sums (DIST), PK_SITE_WINDOW: a gather window outside the flag array (status FEM_PCG_BAD_WINDOW)
-// (PK_SITE_WINDOW, pk_window_bad, pk_fail_status: common.hpp)
-__device__ __forceinline__ bool pk_wait_ge(const unsigned* p, unsigned target, unsigned* tmo) {
-    const uint64_t t0 = pk_now();
-    for (unsigned spins = 0;; ++spins) {
-        if (pk_ld(p) >= target) return true;
-        if ((spins & 63) == 63 && pk_ld(tmo)) return false;
-        if ((spins & 63) == 63 && pk_expired(t0, PK_WAIT_TICKS)) {
-            pk_st(tmo, 1u + 16u * (target / NXCD));
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(2);
-    }
-}
-
-// fixed-order sum of n sc1-loaded partials by one wave (identical result in every lane)
-__device__ __forceinline__ double pk_sum(const double* part, int n) {
-    const int lane = threadIdx.x & 63;
-    double v = 0.0;
-    for (int i = lane; i < n; i += 64) v += __hip_atomic_load(part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return wave_sum(v);
-}
-
-// grid barrier of epoch e over 8 groups of nper workgroups, then the fixed-order sums of the partial vectors pd
-// (and pg when given) by wave 0 alone, handed to the other waves through LDS (out[0], out[1]). One wave per
-// workgroup reads the G partials instead of all 16 (4,096 waves loading the same 4 KB with sc1 loads queue on the
-// memory channels that hold those lines).
-// entry_sync = false: the caller's own workgroup barrier (pk_block_sum's) already separates every wave's prior work
-__device__ __forceinline__ bool pk_barrier(unsigned* sy, int grp, unsigned nper, unsigned e, int* lds_ok,
-                                           const double* pd, const double* pg, int G, double* out,
-                                           bool entry_sync = true) {
-    if (entry_sync) __syncthreads();
-    if (threadIdx.x < 64) {
-        int okv = 0;
-        if (threadIdx.x == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            unsigned* tmo = sy + PK_TMO;
-            bool ok;
-            const unsigned old = __hip_atomic_fetch_add(sy + PK_GRP + grp * PK_LINE, 1u, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT);
-            // last of its group: arrive on all 8 replicas of the top counter (one line each); every workgroup polls
-            // its group's replica (32 pollers per line, no leader -> generation hop)
-            if (old == e * nper - 1)
-                for (int r = 0; r < NXCD; ++r)
-                    __hip_atomic_fetch_add(sy + PK_GEN + r * PK_LINE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = pk_wait_ge(sy + PK_GEN + grp * PK_LINE, e * NXCD, tmo);
-            okv = ok ? 1 : 0;
-        }
-        okv = __builtin_amdgcn_readfirstlane(okv);
-        if (okv && pd) {   // both partial vectors in one round of loads (same per-lane order as two pk_sums)
-            const int lane = threadIdx.x & 63;
-            double vd = 0.0, vg = 0.0;
-            if (pg) {
-#pragma unroll 4
-                for (int i = lane; i < G; i += 64) {
-                    const double a = __hip_atomic_load(pd + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const double b = __hip_atomic_load(pg + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    vd += a;
-                    vg += b;
-                }
-            } else {
-#pragma unroll 4
-                for (int i = lane; i < G; i += 64) vd += __hip_atomic_load(pd + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            const double d = wave_sum(vd);
-            const double g = pg ? wave_sum(vg) : 0.0;
-            if (threadIdx.x == 0) {
-                out[0] = d;
-                out[1] = g;
-            }
-        }
-        if (threadIdx.x == 0) *lds_ok = okv;
-    }
-    __syncthreads();
-    return *lds_ok != 0;
-}
-
-// fixed-order workgroup sum (PK_WAVES waves), valid in thread 0
-__device__ __forceinline__ double pk_block_sum(double v, double* lds16) {
-    v = wave_sum(v);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) lds16[w] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < PK_WAVES; ++i) t += lds16[i];
-    }
-    return t;
-}
 
 constexpr int PK_MAX_RANKS = 8;
 
@@ -224,6 +78,9 @@ struct PkArgs {
     const double* vals_full;   // the shared values and lists: the overflow slices of the OVF build read these
     const int16_t* ucol_full;
     const PkDesc* desc;        // DESC build (FEM_TUNE_PK_DESC): one record per slice of the diagonal-free stream
+    pk_u64* gran;              // GRAN builds (FEM_TUNE_PK_GRAN): the granule block [2 banks][G][PK_GRAN_STRIDE], d and g
+                               // are reduced through it (pcg_persist_sync.hpp) and the group counters stay
+                               // untouched; nullptr for every other build
 };
 
 // a product rounded on its own: the empty asm keeps the compiler from contracting it into a later add (an fma of
@@ -357,8 +214,13 @@ __device__ __forceinline__ void pk_publish_flag(const PkArgs& a, int Lg, unsigne
 // record (sell_pair.hpp PkDesc) by scalar loads instead of three dependent vector loads and the delta words of every
 // round. The record of the next slot is requested before the current slot's rounds, that of the sweep's first slot
 // before the u-flag wait (it does not depend on u). Slices of kind PKD_LANE run the OD build's path.
-template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false, bool OD = false, bool DESC = false>
+// GRAN: d and g are reduced through tagged granules (PkArgs::gran, pcg_persist_sync.hpp) instead of pk_barrier. A
+// build of its own, not a run-time branch: with both reductions in one kernel the seven-slot builds spill 100 bytes
+// more per lane
+template <int MAXS, bool PROF, bool GSC1, bool OVF = false, bool DIST = false, bool OD = false, bool DESC = false,
+          bool GRAN = false>
 __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
+    static_assert(!(GRAN && DIST), "granule reduction: single-GPU builds (the DIST barrier carries the rank exchange)");
     static_assert(!DIST || (GSC1 && !OVF), "distributed persistent PCG: sc1 gathers, no overflow build");
     static_assert(!(DIST && OD), "distributed persistent PCG: no diagonal-free stream");
     static_assert(!DESC || (OD && GSC1 && !OVF), "descriptor records: the diagonal-free sc1 builds without overflow");
@@ -378,6 +240,7 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
     double* lds16 = pk_lds_raw;
     int& lds_ok = *reinterpret_cast<int*>(pk_lds_raw + PK_WAVES);
     double* lds_dg = pk_lds_raw + PK_WAVES + 2;   // barrier sums (bytes 144..159 of the 256-byte head)
+    static_assert(PKG_OK2 * sizeof(int) == 32, "granule build: the second verdict word sits at byte 160 of the head");
     double* pk_lds = pk_lds_raw + PK_LDS_HEAD / sizeof(double);
     const int G = gridDim.x;
     const unsigned nper = (unsigned)(G / NXCD);
@@ -411,6 +274,7 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
     double* wl = pk_lds + PK_WAVES * MAXS * 64 + wv * MAXS * 64 + lane;
     double* vl = pk_lds + 2 * PK_WAVES * MAXS * 64 + wv * PK_VL * 64 + lane;   // v of slots j < PK_VL
     unsigned* sy = a.sync;
+    pk_u64* const gran = GRAN ? a.gran : nullptr;   // (the host passes the block to GRAN builds and to no other)
     PcgState* st = a.st;
     // u-flags: this rank's own lines (single GPU), or the comm block's lines of all ranks' workgroups (DIST)
     unsigned* uf = DIST ? reinterpret_cast<unsigned*>(a.peer[a.rank] + a.off_flag) : sy + PK_UFLAG;
@@ -694,10 +558,17 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
             PK_MARK(2);
             // (An L2 prefetch of the next SpMV's first slice by the non-polling waves here, under the grid barrier,
             // measured slower, 45.3-45.6 against 44.6-44.9 us per iteration: profiles/r06v_persist_l2_prefetch_ab.txt.)
-            if (threadIdx.x == 0) __hip_atomic_store(pd + L, dsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // (pk_block_sum ended on a workgroup barrier: the grid barrier needs no entry barrier of its own)
-            if (!(DIST ? pk_barrier_dist(a, sy, grp, nper, e, &lds_ok, pd, k > 0 ? pd + G : nullptr, G, lds_dg, false)
-                       : pk_barrier(sy, grp, nper, e, &lds_ok, pd, k > 0 ? pd + G : nullptr, G, lds_dg, false))) {
+            bool okb;
+            if (GRAN) {   // the d granules of epoch e; the g granules of this bank were tagged e by the last update
+                if (threadIdx.x == 0) pk_gran_put(pk_gran_at(gran, G, L, e, 0), e, dsum);
+                okb = pk_gran_reduce(gran, sy, e, &lds_ok, G, k > 0 ? PKG_DG : PKG_D, lds_dg, false);
+            } else {
+                if (threadIdx.x == 0) __hip_atomic_store(pd + L, dsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                okb = DIST ? pk_barrier_dist(a, sy, grp, nper, e, &lds_ok, pd, k > 0 ? pd + G : nullptr, G, lds_dg, false)
+                           : pk_barrier(sy, grp, nper, e, &lds_ok, pd, k > 0 ? pd + G : nullptr, G, lds_dg, false);
+            }
+            if (!okb) {
                 fail = true;
                 break;
             }
@@ -820,8 +691,11 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
                 double gsum = 0.0;
 #pragma unroll
                 for (int i = 0; i < PK_WAVES; ++i) gsum += lds16[i];
-                __hip_atomic_store(a.part + (size_t)(bank ^ 1) * 2 * G + G + L, gsum, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+                if (GRAN)
+                    pk_gran_put(pk_gran_at(gran, G, L, e + 1, 2), e + 1, gsum);
+                else
+                    __hip_atomic_store(a.part + (size_t)(bank ^ 1) * 2 * G + G + L, gsum, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
                 pk_st(uf + Lg * PK_LINE, e);
                 if constexpr (DIST) {
                     if (pubmask) {   // rows published to other GPUs (every wave drained them): one system release
@@ -855,8 +729,9 @@ __global__ void __launch_bounds__(PK_T) k_pcg_persist(PkArgs a) {
     if (!fail && !halt && k == a.kmax && a.kmax > 0) {
         const unsigned e = ebase + (unsigned)a.kmax + 1;
         const double* pgl = a.part + (size_t)(a.kmax & 1) * 2 * G + G;
-        const bool okb = DIST ? pk_barrier_dist(a, sy, grp, nper, e, &lds_ok, pgl, nullptr, G, lds_dg)
-                              : pk_barrier(sy, grp, nper, e, &lds_ok, pgl, nullptr, G, lds_dg);
+        const bool okb = GRAN   ? pk_gran_reduce(gran, sy, e, &lds_ok, G, PKG_G, lds_dg)   // the g granules tagged e
+                         : DIST ? pk_barrier_dist(a, sy, grp, nper, e, &lds_ok, pgl, nullptr, G, lds_dg)
+                                : pk_barrier(sy, grp, nper, e, &lds_ok, pgl, nullptr, G, lds_dg);
         if (!okb) {
             fail = true;
         } else {

@@ -1879,6 +1879,13 @@ class PcgRunner:
         C.check(self.lib.fem_pcg_pipelined(self.h, ctypes.byref(on)), "fem_pcg_pipelined")
         return bool(on.value)
 
+    def persist_granules(self):
+        """True when the started context's persistent launches reduce d and g through tagged granules
+        (include/fem355.h FEM_TUNE_PK_GRAN), False on the counter barrier."""
+        on = ctypes.c_int()
+        C.check(self.lib.fem_pcg_persist_granules(self.h, ctypes.byref(on)), "fem_pcg_persist_granules")
+        return bool(on.value)
+
     def persist_build(self):
         """(register slots per wave, overflow build, packed slices per wave) of the persistent launches (after
         start(); zeros when the context does not run schedule 3)."""

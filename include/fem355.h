@@ -424,7 +424,7 @@ int fem_pcg_poll(fem_pcg* s, int* iters, int* status, double* rz);
  * test. FEM_EARG when the context has no window array */
 int fem_pcg_debug_window(fem_pcg* s, int L, int lo, int hi);
 /* [sync] diagnostic of a FEM_PCG_SYNC_TIMEOUT: the give-up site code (persistent kernel: 1 grid barrier, 2 u-flag
- * window, 3 rank sums of the DIST build, + 16 * epoch; merged update k_pcg_update2: 4 + 16 * launch since start),
+ * window, 3 rank sums of the DIST build, 5 granule reduction, + 16 * epoch; merged update k_pcg_update2: 4 + 16 * launch since start),
  * 0 for any other status */
 int fem_pcg_sync_site(fem_pcg* s, int* site);
 /* [sync] out6 = {rz (rs_old), pq (p.Ap), alpha, beta, rz_new, completed iterations} for the host messages */
@@ -553,6 +553,9 @@ int fem_pcg_set_layout(fem_pcg* s, const double* svals, const int16_t* pcols, co
  * 3): register slots per wave (bs = 1: 1, 2, 4 or 7; bs = 3: 2), 1 for the overflow build, and the packed
  * assignment's slices per wave (0: the even spread) */
 int fem_pcg_persist_build(fem_pcg* s, int* slots, int* overflow, int* pack);
+/* 1 in *on when the started context's persistent launches reduce d and g through tagged granules
+ * (FEM_TUNE_PK_GRAN), 0 when they run the counter barrier or the schedule is not 3 */
+int fem_pcg_persist_granules(fem_pcg* s, int* on);
 /* 1 in *on when the started context runs the pipelined persistent iteration (FEM_TUNE_PK_GV), else 0 */
 int fem_pcg_pipelined(fem_pcg* s, int* on);
 /* persistent schedule only: k iterations of the instrumented kernel build; host_out[G * 8] = per-workgroup shader-clock
@@ -580,7 +583,7 @@ int fem_enforce_constraints(double* x, double* r, int64_t n, int order, int64_t 
                             int64_t G, const int64_t* r3_ptr, const int64_t* r3_master, const double* r3_wsum,
                             const int64_t* r3_slave, const double* r3_w, fem_stream_t stream);
 /* tuning flags (default FEM_TUNE_REVERSE | FEM_TUNE_PAIR | FEM_TUNE_PK_SC1 | FEM_TUNE_PK_PACK | FEM_TUNE_PK_UNI |
- * FEM_TUNE_UPD1 | FEM_TUNE_PK_OFFDIAG | FEM_TUNE_PK_DESC): the SpMV of every schedule sweeps each XCD's slice range backwards on
+ * FEM_TUNE_UPD1 | FEM_TUNE_PK_OFFDIAG | FEM_TUNE_PK_DESC | FEM_TUNE_PK_GRAN): the SpMV of every schedule sweeps each XCD's slice range backwards on
  * odd iterations, so the matrix tail read last (still in the MI355X's 256 MB memory-side cache) is read first by
  * the next sweep: 67 -> 57 us per SpMV on the 10M Poisson matrix. Results depend on the flags only through the
  * order of the per-block p.q partials (deterministic for a given flag set). */
@@ -588,7 +591,24 @@ enum { FEM_TUNE_REVERSE = 1, FEM_TUNE_PAIR = 2, FEM_TUNE_PK_SC1 = 4, FEM_TUNE_PK
        FEM_TUNE_PK_COOP = 32, FEM_TUNE_DIST_FINE = 64, FEM_TUNE_PK_UNI = 128, FEM_TUNE_PK_WIDE = 256,
        FEM_TUNE_DIST_DROP = 512, FEM_TUNE_UPD1 = 1024, FEM_TUNE_U2_HOLD = 2048, FEM_TUNE_U2_SMALL = 4096,
        FEM_TUNE_MF_GATHER = 8192, FEM_TUNE_PK_GV = 16384, FEM_TUNE_PK_OFFDIAG = 32768,
-       FEM_TUNE_PK_DESC = 65536 };
+       FEM_TUNE_PK_DESC = 65536, FEM_TUNE_PK_GRAN = 131072, FEM_TUNE_PK_GRAN_SMALL = 262144 };
+/* FEM_TUNE_PK_GRAN_SMALL (opt-in, with FEM_TUNE_PK_GRAN): the granule reduction also in the two- and four-slot builds
+ * (2 to 4 packed slices per wave: about 0.2M to 1M rows on 256 workgroups). Measured there it is slower than the
+ * counter barrier (two slots: 10.1 against 9.5 us per iteration) or no faster (four slots), so those builds keep the
+ * barrier by default; same bits either way. */
+/* FEM_TUNE_PK_GRAN (default): persistent schedule, bs = 1, single GPU, not the pipelined build, and only the builds
+ * the default flag set reaches: those with FEM_TUNE_PK_DESC, FEM_TUNE_PK_OFFDIAG and FEM_TUNE_PK_SC1 all on (1 and 7
+ * slots and the instrumented one; 2 and 4 slots with FEM_TUNE_PK_GRAN_SMALL) and the overflow build with
+ * FEM_TUNE_PK_OFFDIAG and FEM_TUNE_PK_SC1. Any
+ * other flag set keeps the counter barrier without notice: fem_pcg_persist_granules tells which reduction a context
+ * runs. With it the per-iteration grid reduction of d = u.Au and g = r.z runs without a barrier: every workgroup
+ * publishes its partials as 8-byte {epoch, half a double} granules (one relaxed agent-scope store each) in a parity
+ * bank; wave 0 of every workgroup re-reads the d records it still misses, and the workgroup's last wave the g records
+ * (published one SpMV phase earlier), until every tag equals the epoch, then sums them in the fixed order of the
+ * counter barrier's sums: bit-identical iterates. Holding every d record of an epoch also tells a workgroup that all
+ * others finished that SpMV, which is what lets it overwrite u. The group counters are never touched; a give-up
+ * reports site 5. The flag may change between launches of a started context: a launch whose reduction differs from
+ * the last one's starts the epochs over (sync words and granules zeroed). */
 /* FEM_TUNE_PK_DESC (default; needs FEM_TUNE_PK_OFFDIAG and FEM_TUNE_PK_SC1, not the overflow build): the pass that
  * writes the diagonal-free stream also writes one 64-byte record per slice -- value base, streamed width, the
  * diagonal's list position and the slice's delta list -- and the kernel reads a slot's record with scalar loads, one
