@@ -695,12 +695,29 @@ __global__ void __launch_bounds__(XD_BLOCK) k_xd_mass(MfOp op, double rho, doubl
     __syncthreads();
     for (int e = tid; e < ne; e += XD_BLOCK) {
         const uint32_t w = op.eloc[e0 + e];
-        double xc[4][3], cf[4][3];
+        // only |det| enters. A chunk's local nodes ascend by global id, so the four local ids sorted are the nodes
+        // in ascending global id: det from them (the form of tet4_det_sorted) is the same bits for any local order
+        // of the element's nodes
+        int n[4] = {(int)(w & 0xff), (int)((w >> 8) & 0xff), (int)((w >> 16) & 0xff), (int)((w >> 24) & 0xff)};
+#define XD_CSWAP(i, j)           \
+    if (n[j] < n[i]) {           \
+        const int t_ = n[i];     \
+        n[i] = n[j];             \
+        n[j] = t_;               \
+    }
+        XD_CSWAP(0, 1) XD_CSWAP(2, 3) XD_CSWAP(0, 2) XD_CSWAP(1, 3) XD_CSWAP(1, 2)
+#undef XD_CSWAP
+        double e1[3], e2[3], e3[3];
 #pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) xc[b][k] = xs[(w >> (8 * b)) & 0xff][k];
-        qe[e] = rho * (fabs(xd_cofactors(xc, cf)) * (1.0 / 6.0)) * 0.25;
+        for (int k = 0; k < 3; ++k) {
+            const double p0 = xs[n[0]][k];
+            e1[k] = xs[n[1]][k] - p0;
+            e2[k] = xs[n[2]][k] - p0;
+            e3[k] = xs[n[3]][k] - p0;
+        }
+        const double det = e1[0] * (e2[1] * e3[2] - e2[2] * e3[1]) + e1[1] * (e2[2] * e3[0] - e2[0] * e3[2]) +
+                           e1[2] * (e2[0] * e3[1] - e2[1] * e3[0]);
+        qe[e] = rho * (fabs(det) * (1.0 / 6.0)) * 0.25;
     }
     __syncthreads();
     if (tid < nn) {

@@ -248,3 +248,223 @@ def test_exact2_calibration_errors():
                     err = X2.iso_calibration_err2(etype, case, q, part)
                     print(f"CALIB {etype} {q} {part} {case}: {err:.2e}")
                     assert err == err and err < 1.0
+
+
+# ----------------------------------------------------------------------------- third generation (tests/exact_ref3.py)
+import exact_ref3 as X3  # noqa: E402
+
+C3D4_QUANTITIES3 = [("xd_" + m, p) for m in X3.XD_MATERIALS for p in ("f", "w")] + \
+    [("mass", None), ("dt", None), ("vol", None), ("energy", "ce"), ("energy", "dct"), ("energy", "c"), ("matvec", None)]
+
+
+def _shell_quantities(etype):
+    q = [("geom", p) for p in X3.SHELL_GEOM_PARTS] + [("K", p) for p in X3.SHELL_K_PARTS if etype == "s4" or p != "points"]
+    return q + [("stress", None), ("apply", None)]
+
+
+def test_exact3_matches_restatements_on_plain_c3d4_mesh():
+    """Unflipped unit mesh: the exact explicit force, energy, lumped mass and step and the exact topopt volumes, unit
+    energy, sensitivities, compliance and scaled product within 1e-12 of explicit_ref, hyperelastic_ref and topopt_ref
+    as their own tests use them."""
+    import explicit_ref as XR
+    import hyperelastic_ref as HR
+    import topopt_ref as TR
+    case = "unflipped"
+    c, t = X.tet4_case(case)
+    for mat in X3.XD_MATERIALS:
+        f, mag, w = X3.tet4_exact3(case, "xd_" + mat)
+        u = X3.xd_u(case, mat)
+        m = XR.Model(c, t, X3.E, X3.NU, mat)
+        assert X.dof_err(m.f_int(u.reshape(-1)).view(-1, 3), f, mag) < RESTATE, mat
+        assert X3.rel_err(m.energy(u.reshape(-1)), w) < RESTATE, mat
+        assert bool((mag >= f.abs()).all()) and w > 0
+        if mat != "linear":
+            hm = HR.Model(c, t, X3.E, X3.NU, mat)
+            assert X.dof_err(hm.f_int(u), f, mag) < RESTATE and X3.rel_err(hm.energies(u).sum(), w) < RESTATE
+    assert X3.node_err(XR.lumped_mass(c, t, X3.RHO), X3.tet4_exact3(case, "mass")) < RESTATE
+    dt, dte = XR.element_dt(c, t, X3.E, X3.NU, X3.RHO)
+    assert X3.node_err(dte, X3.tet4_exact3(case, "dt")) < RESTATE and dt == float(dte.min())
+    m = TR.Model(c, t, X3.E, X3.NU)
+    rho_t = X3.to_rho_t(t.shape[0])
+    assert 0.2 <= float(rho_t.min()) and float(rho_t.max()) <= 1.0
+    s = TR.simp(rho_t, X3.PENAL, X3.S_MIN)
+    assert X3.node_err(s, X.to_tensor(X3.simp_fr(rho_t))) < AGREE
+    ce_ex, dct_ex, c_ex = X3.tet4_exact3(case, "energy")
+    ce = m.unit_energy(X.tet4_u(case).reshape(-1))
+    assert X3.node_err(m.V, X3.tet4_exact3(case, "vol")) < RESTATE and X3.node_err(ce, ce_ex) < RESTATE
+    dct = -X3.PENAL * (1.0 - X3.S_MIN) * rho_t ** (X3.PENAL - 1.0) * X3.E * ce
+    assert X3.node_err(dct, dct_ex) < RESTATE and X3.rel_err((s * X3.E * ce).sum(), c_ex) < RESTATE
+    y_ex, mag = X3.tet4_exact3(case, "matvec")
+    assert X.dof_err(m.dense(s) @ X.tet4_x(case, "elastic").reshape(-1), y_ex, mag) < RESTATE
+    for q, part in C3D4_QUANTITIES3:
+        assert X3.tet4_calibration_err3(case, q, part) < RESTATE, (q, part)
+
+
+def test_exact3_matches_shell_ref_and_the_recorded_elements():
+    """Plain patch: every exact shell quantity within 1e-12 of tests/shell_ref.py. The eight recorded elements of
+    tests/golden/shell_cells.npz per family: exact K, the s4 points' terms, frames, local coordinates, J and gradients
+    within 1e-12 of the recording."""
+    import shell_ref as SR
+    from conftest import load_golden
+    for etype in X3.SHELL_TYPES:
+        for q, part in _shell_quantities(etype):
+            assert X3.shell_calibration_err(etype, "plain", q, part) < RESTATE, (etype, q, part)
+    g = load_golden("shell_cells")
+    mem, ben = X3.shell_params()
+    assert torch.equal(mem, g["membrane"]) and torch.equal(ben, g["bending"])
+    Xr = X._rows(g["coords"])
+    for etype in X3.SHELL_TYPES:
+        Ks, Ps, units, locs = [], [], [], []
+        for el in g[etype].tolist():
+            xe = [Xr[n] for n in el]
+            terms, unit = X3.shell_K_terms_fr(xe)
+            Ks.append(X3._sum_terms(terms))
+            Ps.append([[[T[i][j] for T in terms] for j in range(len(Ks[-1]))] for i in range(len(Ks[-1]))])
+            units.append(unit)
+            locs.append(X3.shell_frame_fr(xe)[1])
+        assert X.elem_err(g[etype + "_K"], X.to_tensor(Ks)) < RESTATE
+        assert X.elem_err(g[etype + "_unit"], X.to_tensor(units)) < RESTATE
+        assert X.elem_err(g[etype + "_local"], X.to_tensor(locs)) < RESTATE
+        if etype == "s4":
+            assert X.elem_err(g["s4_K_points"], X.to_tensor(Ps)) < RESTATE
+            for p, f in enumerate(SR.k_factors()):
+                Jg = [X3.shell_point_fr(loc, f) for loc in locs]
+                assert X.elem_err(g["s4_J"][..., p], X.to_tensor([o[0] for o in Jg])) < RESTATE
+                assert X.elem_err(g["s4_grads"][..., p], X.to_tensor([o[2] for o in Jg])) < RESTATE
+        else:
+            Jg = [X3.shell_point_fr(loc) for loc in locs]
+            assert X.elem_err(g["s3_J"], X.to_tensor([o[0] for o in Jg])) < RESTATE
+            assert X.elem_err(g["s3_grads"], X.to_tensor([o[2] for o in Jg])) < RESTATE
+
+
+def _shell_aspect(c, conn):
+    """Longest edge squared over twice the area of the (first) triangle / the area spanned by the quad's diagonals."""
+    x = c[conn]
+    npe = conn.shape[1]
+    L2 = max(float(((x[:, (k + 1) % npe] - x[:, k]) ** 2).sum(1).max()) for k in range(npe))
+    if npe == 3:
+        area2 = torch.cross(x[:, 1] - x[:, 0], x[:, 2] - x[:, 0], dim=1).norm(dim=1)
+    else:
+        area2 = 0.5 * torch.cross(x[:, 2] - x[:, 0], x[:, 3] - x[:, 1], dim=1).norm(dim=1)
+    lmax2 = torch.stack([((x[:, (k + 1) % npe] - x[:, k]) ** 2).sum(1) for k in range(npe)], 1).max(1).values
+    assert L2 == float(lmax2.max())
+    return lmax2 / area2
+
+
+def test_cases3_are_what_they_claim():
+    """The c3d4 cases hold 81 negative dets (and "unflipped" none). The shell cases: 72 s4 / 144 s3 elements on 90
+    nodes, every second element started one place further round, every quad non-planar in exact arithmetic (plain:
+    node 2 lies at least 1e-4 of the element's size off the plane of the frame), aspect ratios below 10 on the
+    well-shaped cases and between 3e3 and 1e5 on the squashed ones, and the shifted patches 1e4 / 1e6 from the
+    origin; the samples hold elements 0, 63, 64, the last and both start orders."""
+    for case in X.TET4_CASES:
+        c, t = X.tet4_case(case)
+        assert int((R.tet4_cofactors(c, t)[1] < 0).sum()) == 81, case
+    assert int((R.tet4_cofactors(*X.tet4_case("unflipped"))[1] < 0).sum()) == 0
+    c0, quads = X3.shell_unit_patch()
+    assert c0.shape == (90, 3) and quads.shape == (72, 4)
+    for etype, M in (("s4", 72), ("s3", 144)):
+        s = X3.SHELL_SAMPLE[etype]
+        assert len(set(s)) == 8 and {0, 63, 64, M - 1} <= set(s) and {e % 2 for e in s} == {0, 1}
+        for case in X3.SHELL_CASES:
+            c, conn = X3.shell_case(etype, case)
+            assert conn.shape == (M, int(etype[1])) and c.shape == (90, 3), (etype, case)
+            base = quads if etype == "s4" else torch.stack([quads[:, [0, 1, 2]], quads[:, [0, 2, 3]]], 1).reshape(M, 3)
+            assert torch.equal(conn[0::2], base[0::2]) and torch.equal(conn[1::2], base[1::2].roll(-1, 1))
+            asp = _shell_aspect(c, conn)
+            if case.startswith("squash"):
+                assert 3e3 < float(asp.min()) and float(asp.max()) < 1e5, (etype, case, float(asp.min()), float(asp.max()))
+            else:
+                assert float(asp.max()) < 10.0, (etype, case, float(asp.max()))
+            if case.startswith("shift"):
+                d = c.norm(dim=1) / float(case[5:])
+                assert 1.2 < float(d.min()) and float(d.max()) < 1.3, (case, float(d.min()))
+            if etype == "s4":
+                Xr = X._rows(c)
+                for el in conn.tolist():
+                    p = [Xr[n] for n in el]
+                    vol = X._dot(X._sub(p[1], p[0]), X._cross(X._sub(p[2], p[0]), X._sub(p[3], p[0])))
+                    assert vol != 0, (case, el)
+    import shell_ref as SR
+    _, loc = SR.geometry(*X3.shell_case("s4", "plain"))
+    assert float((loc[:, 2, 2].abs() / loc[:, :, :2].abs().amax((1, 2))).min()) > 1e-4
+
+
+def test_stable_step_reference_is_below_the_dense_bound():
+    """Where the dense eigenproblem is well conditioned (flipped, shift1e4, scale1e-3, scale1e3) the exact element
+    step's minimum is below 2 / omega_max of explicit_ref's lumped-mass pencil: the GPU test asserts it of the device."""
+    import explicit_ref as XR
+    for case in ("flipped", "shift1e4", "scale1e-3", "scale1e3"):
+        c, t = X.tet4_case(case)
+        dt = float(X3.tet4_exact3(case, "dt").min())
+        bound = 2.0 / XR.omega_max(c, t, X3.E, X3.NU, X3.RHO)
+        assert 0.0 < dt <= bound and dt > 0.25 * bound, (case, dt, bound)
+
+
+def _s4_frame_b_from_node_2(coords, conn):
+    import shell_ref as SR
+    return SR.frame(coords, conn[:, [0, 1, 3, 2]])
+
+
+def _gradients_transposed(local, f=None):
+    import shell_ref as SR
+    dxi, det = SR.param_derivs(local.shape[1], f)
+    Ji = torch.inverse(SR.jacobian(local, f))
+    return torch.einsum("mba,nb->mna", Ji, torch.stack([dxi, det], -1))
+
+
+def test_comparator_fails_wrong_restatements3():
+    """exact_ref.check at 8 x the calibration error rejects: an explicit force with the signed volume V = det / 6, a
+    lumped mass with det for |det|, a stable step without g_0 (half-flipped c3d4 mesh); an s4 frame whose b comes from
+    node 2 and gradients contracted with J^-T for the reference's J^-1 (plain shell patch). The calibration forms
+    themselves pass."""
+    import shell_ref as SR
+    case = "flipped"
+    c, t = X.tet4_case(case)
+    det, g = X.tet4_geom_edges_fp64(c, t)
+    for mat in X3.XD_MATERIALS:
+        f_ex, mag, _ = X3.tet4_exact3(case, "xd_" + mat)
+        cal = X3.tet4_calibration_err3(case, "xd_" + mat, "f")
+        u = X3.xd_u(case, mat)
+        X.check("edges", X.dof_err(X3.force_fp64(c, t, u, mat, det.abs() / 6.0, g)[0], f_ex, mag), cal)
+        with pytest.raises(AssertionError):
+            X.check("signed volume", X.dof_err(X3.force_fp64(c, t, u, mat, det / 6.0, g)[0], f_ex, mag), cal)
+    with pytest.raises(AssertionError):
+        X.check("mass with det", X3.node_err(X3.mass_fp64(c, t, det / 6.0), X3.tet4_exact3(case, "mass")),
+                X3.tet4_calibration_err3(case, "mass"))
+    with pytest.raises(AssertionError):
+        X.check("step without g_0", X3.node_err(X3.dt_fp64(g[:, 1:]), X3.tet4_exact3(case, "dt")),
+                X3.tet4_calibration_err3(case, "dt"))
+    c, conn = X3.shell_case("s4", "plain")
+    ex = X3.shell_exact("s4", "plain", "geom")
+    X.check("frame", X.elem_err(SR.frame(c, conn), ex[0]), X3.shell_calibration_err("s4", "plain", "geom", "unit"))
+    with pytest.raises(AssertionError):
+        X.check("b from node 2", X.elem_err(_s4_frame_b_from_node_2(c, conn), ex[0]),
+                X3.shell_calibration_err("s4", "plain", "geom", "unit"))
+    for etype in X3.SHELL_TYPES:
+        c, conn = X3.shell_case(etype, "plain")
+        f = None if etype == "s3" else X3.shell_geom_factors()
+        _, loc = SR.geometry(c, conn)
+        with pytest.raises(AssertionError):
+            X.check("J^-T", X.elem_err(_gradients_transposed(loc, f), X3.shell_exact(etype, "plain", "geom")[3]),
+                    X3.shell_calibration_err(etype, "plain", "geom", "grads"))
+
+
+def test_exact3_calibration_errors():
+    """The calibration errors of every (quantity, case) of the third generation. c3d4: the restatements on
+    edge-difference gradients stay below 1e-14 on every case but the rotated sliver. Shells: shell_ref stays below
+    1e-14 off the squashed cases (it differences from node 0, so a shift costs nothing) and loses what the projection
+    b - (a.b / a.a) a of a 1e4 : 1 sliver loses, 1e-11, on them."""
+    for case in X.TET4_CASES:
+        for q, part in C3D4_QUANTITIES3:
+            err = X3.tet4_calibration_err3(case, q, part)
+            print(f"CALIB c3d4 {q} {part} {case}: {err:.2e}")
+            assert err == err and err < 1.0
+            if case != "squash1e-4_rot":
+                assert err < C3D4_CALIBRATION, (case, q, part, err)
+    for etype in X3.SHELL_TYPES:
+        for case in X3.SHELL_CASES:
+            for q, part in _shell_quantities(etype):
+                err = X3.shell_calibration_err(etype, case, q, part)
+                print(f"CALIB {etype} {q} {part} {case}: {err:.2e}")
+                assert err == err and err < (1e-10 if case.startswith("squash") else C3D4_CALIBRATION), (etype, case, q)
