@@ -1,8 +1,14 @@
 """Node renumbering (opt-in RCM, csrc/reorder.hip) -- CPU tier: the oracle's rule (oracle/rcm_ref.py) gives a
 permutation, undoes a random numbering of the Kuhn cube down to the bandwidth of scipy's reverse Cuthill-McKee, and
 handles several components and nodes no element touches. The device implementation equals this oracle exactly
-(tests/test_gpu_reorder.py)."""
+(tests/test_gpu_reorder.py).
+
+The level-by-level restatement of the same rule (tests/rcm_levels_ref.py), which stands in for the oracle where the
+oracle's Python edge walk is too slow, equals the oracle exactly on every graph family of the edge tests
+(tests/test_gpu_reorder_edges.py) up to the 262,145-wide one, and every family reaches the kernel path it is there
+for, by the restatement's level structure."""
 import numpy as np
+import pytest
 import scipy.sparse as sp
 from scipy.sparse.csgraph import reverse_cuthill_mckee
 import torch
@@ -11,6 +17,7 @@ import fem355  # noqa: F401
 from fem355 import mesh
 from oracle import ref_cpu as R
 from oracle import rcm_ref
+import rcm_levels_ref as L
 
 
 def _permuted_cube(n, seed):
@@ -58,3 +65,19 @@ def test_rcm_oracle_components_and_unused_nodes():
     # each component is contiguous in the new numbering
     new_first = inv[:N1]
     assert new_first.max() - new_first.min() == N1 - 1
+
+
+@pytest.mark.parametrize("name", [n for n in L.NAMES if n != "spoked-1048577"])
+def test_level_restatement_equals_oracle(name):
+    """The 1,048,577-wide case is left to the restatement alone (the oracle's edge walk takes too long there)."""
+    _, N, rp, ci, s = L.case(name)
+    perm, inv = rcm_ref.rcm(rp, ci, N)
+    assert np.array_equal(s.perm, perm) and np.array_equal(s.inv, inv)
+    assert sum(int(c.sum()) for comp in s.counts for c in comp) + s.components == sum(map(sum, s.widths))
+
+
+@pytest.mark.parametrize("name", L.NAMES)
+def test_edge_families_reach_their_regime(name):
+    _, N, rp, _, s = L.case(name)
+    assert np.array_equal(np.sort(s.perm), np.arange(N)) and np.array_equal(s.inv[s.perm], np.arange(N))
+    L.assert_regime(name, N, rp, s)
